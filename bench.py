@@ -11,8 +11,13 @@ max-over-ranks wall time of the timed steps (weak scaling: replicas per GPU fixe
 
 Run: python bench.py [--gpus N --steps K --warmup W]; N > 1 under torch.distributed.run, or
 bench.py --gpus N alone, which starts the N rank processes itself (one rank per GPU, RCCL
-all-reduce of the shared nets' gradients). The line also carries the env step kernel alone
-(pre-sampled actions, seeds {0,1,2}) as "step_kernel".
+all-reduce of the shared nets' gradients).
+
+A plain run sets up, warms up, times the K steps and prints the result line (the env launch's
+roofline entry in it comes from spans recorded inside the timed steps). --dump-outputs DIR also
+writes what the last timed step computed as DIR/<name>.npy (dump_outputs). --full adds what takes
+runs of its own: the acting launch's roofline ("act_roofline"), the env step kernel alone (SURVEY
+8(d)(i): pre-sampled actions, seeds {0,1,2}) as "step_kernel", and the CPU baselines.
 """
 from __future__ import annotations
 
@@ -206,6 +211,63 @@ def cpu_baseline_e1(seconds_budget: float = 10.0):
                       "reference loop's call pattern) + the C oracle's env step; no update in the sample" % rounds}
 
 
+DUMP_ROWS = 4096             # rows of a large output kept by --dump-outputs (a fixed, seeded sample)
+DUMP_MAX_BYTES = 64 << 20    # all files of one --dump-outputs together
+
+
+def dump_outputs(tr, losses, directory):
+    """What the trainer's last iteration computed, as <directory>/<name>.npy (float32; int32 rewards
+    as float64, exact): the losses iteration() returned, every net's weights after the update, and
+    of the rollout it trained on the actions, log-probs and rewards of every unit, the price
+    chooser's inputs, the observations the next iteration starts from and the last round's agent and
+    auctioneer rewards. An output of more than DUMP_ROWS rows (round x replica, or replica) is
+    written as the same DUMP_ROWS rows every time (drawn once from numpy's default_rng(0), ascending;
+    the row numbers go to rows_<n>.npy), so two builds run with the same arguments compare file by
+    file."""
+    import torch
+
+    os.makedirs(directory, exist_ok=True)
+    picks, total = {}, 0
+
+    def put(name, x, rows=None):
+        nonlocal total
+        x = x.detach()
+        if rows is not None:  # the leading `rows` dims are the rows
+            x = x.reshape((-1,) + tuple(x.shape[rows:]))
+            n = x.shape[0]
+            if n > DUMP_ROWS:
+                if n not in picks:
+                    picks[n] = np.sort(np.random.default_rng(0).choice(n, DUMP_ROWS, replace=False))
+                x = x.index_select(0, torch.from_numpy(picks[n]).to(x.device))
+        a = x.cpu().numpy()
+        a = a.astype(np.float64 if a.dtype in (np.int32, np.int64, np.float64) else np.float32)
+        total += a.nbytes
+        np.save(os.path.join(directory, name + ".npy"), a)
+
+    T = tr.T
+    for u in tr.units():
+        put("loss_" + u.name, losses[u.name])
+        for k, p in u.group.policy.named_parameters():
+            put("weights_%s_%s" % (u.name, k), p)
+        put("rollout_%s_actions" % u.name, u.actions, rows=2)      # [T][E][U] -> rows (t, e)
+        put("rollout_%s_logprobs" % u.name, u.logprobs, rows=2)
+        put("rollout_%s_rewards" % u.name, u.rewards, rows=2)
+    if tr.price_obs is not None:
+        put("rollout_price_states", tr.price_obs, rows=2)
+    if tr.compact:
+        put("next_acceptor_rows", tr.acc_rows[T], rows=1)           # [E][C][stride] -> rows e
+        put("next_acceptor_owner", tr.acc_owner[T], rows=1)
+    else:
+        put("next_acceptor_obs", tr.acc_obs[T], rows=1)
+    put("next_offer_obs", tr.off_obs[T], rows=1)
+    put("agent_reward", tr.agent_reward, rows=1)
+    put("auctioneer_reward", tr.auct_reward, rows=1)
+    for n, idx in picks.items():
+        put("rows_%d" % n, torch.from_numpy(idx))
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit("--dump-outputs wrote %d bytes, more than %d" % (total, DUMP_MAX_BYTES))
+
+
 ROLLOUT_STREAMS = 1   # replica parts on separate HIP streams in the rollout (Trainer rollout_streams)
 SAMPLE_EVERY = 8      # rounds between timed env launches
 
@@ -315,7 +377,8 @@ def bench_other(args):
     tm = dict(tr.timings)
     result["breakdown_ms_per_step"] = {k: v / args.steps * 1e3 for k, v in tm.items()}
     if args.config == "cfg5":
-        result["roofline"] = bdqn_act_roofline(tr, device)
+        if args.full:
+            result["roofline"] = bdqn_act_roofline(tr, device)
     else:
         per_iter_us = [tr.launch_spans_us(span_hist[i]) for i in range(args.steps)]
         launch_us = [v for it in per_iter_us for v in it]
@@ -330,9 +393,10 @@ def bench_other(args):
                 "each round also holds round t+1's acting (offer + acceptor units from the observations in its "
                 "LDS); bytes are the env round's alone" +
                 ("; one launch runs all %d rounds: avg_launch_us = its span / %d" % (tr.T, tr.T) if whole else ""))
-        result["act_roofline"] = act_roofline(tr, device)
-        if getattr(tr, "fused_step", False):
-            result["act_roofline"]["rollout_use"] = "round 0 only; rounds 1..T-1 act inside the env launch"
+        if args.full:
+            result["act_roofline"] = act_roofline(tr, device)
+            if getattr(tr, "fused_step", False):
+                result["act_roofline"]["rollout_use"] = "round 0 only; rounds 1..T-1 act inside the env launch"
     if rank == 0:
         print(json.dumps(result))
     if world > 1:
@@ -636,18 +700,27 @@ def main():
     ap.add_argument("--gpus", type=int, default=None,
                     help="ranks (one per GPU); without a launcher's WORLD_SIZE, N > 1 starts N rank processes")
     ap.add_argument("--stub", action="store_true", help="launcher / process-group check on CPU (gloo), no GPU work")
-    ap.add_argument("--no-step-kernel", action="store_true", help="skip the env-step-kernel-only line")
-    ap.add_argument("--steps", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="also what takes runs of its own: the acting roofline, the env-step-kernel-only line and "
+                         "the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (cfg3, rank 0)")
+    ap.add_argument("--no-step-kernel", action="store_true", help="with --full: skip the env-step-kernel-only line")
+    ap.add_argument("--steps", type=int, default=2, help="timed steps")
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--envs", type=int, default=None, help="env replicas per GPU (default: the config's per-GPU share)")
     ap.add_argument("--update-step", type=int, default=200)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--no-graph", action="store_true", help="eager rollout instead of HIP-graph replay")
     ap.add_argument("--rollout-streams", type=int, default=ROLLOUT_STREAMS,
                     help="replica parts stepped on separate HIP streams (env of one part beside act of another)")
     ap.add_argument("--config", default="cfg3", choices=["cfg2", "cfg3", "cfg4", "cfg5"],
                     help="BASELINE config (cfg3 = the headline; cfg2/cfg4/cfg5 are the other BASELINE workloads)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.config != "cfg3" and not args.stub:
+        ap.error("--dump-outputs covers the headline workload (cfg3)")
     if args.gpus is not None and args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))  # nothing has touched the GPU in this process
     if args.stub:
@@ -692,13 +765,15 @@ def main():
     span_hist = torch.zeros((args.steps,) + tuple(sampled.shape), dtype=sampled.dtype, device=device)
     t0 = time.perf_counter()
     for i in range(args.steps):
-        tr.iteration()
+        losses = tr.iteration()
         span_hist[i].copy_(sampled)
     torch.cuda.synchronize(device)
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize(device)
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(tr, losses, args.dump_outputs)
     timings = dict(tr.timings)
     per_iter_us = [tr.launch_spans_us(span_hist[i]) for i in range(args.steps)]
     launch_us = [v for it in per_iter_us for v in it]
@@ -785,15 +860,16 @@ def main():
                             + (", %d streams" % args.rollout_streams if args.rollout_streams > 1 else ""),
         },
     }
-    result["act_roofline"] = act_roofline(tr, device)
-    if fused:
-        result["act_roofline"]["rollout_use"] = ("round 0 only; rounds 1..T-1 act inside the rollout launch "
-                                                 "(k_env_rollout_act_free, one wave per agent)")
-    if not args.no_step_kernel:
+    if args.full:
+        result["act_roofline"] = act_roofline(tr, device)
+        if fused:
+            result["act_roofline"]["rollout_use"] = ("round 0 only; rounds 1..T-1 act inside the rollout launch "
+                                                     "(k_env_rollout_act_free, one wave per agent)")
+    if args.full and not args.no_step_kernel:
         del tr  # the trainer's rings are not needed by the step-kernel run
         torch.cuda.empty_cache()
         result["step_kernel"] = step_kernel_line(args.envs, device, world, rank)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         try:
             result["cpu_baseline"] = cpu_baseline()
         except Exception as exc:  # reported, never fatal for the GPU number

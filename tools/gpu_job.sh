@@ -6,8 +6,8 @@
 #   gputest             the whole -m gpu suite                         -> gputest.log
 #   tests:<k-expr>      the -m gpu tests matching a pytest -k expression -> tests.log
 #   smoke               __graft_entry__.smoke()                         -> smoke.log
-#   bench[:<args>]      the default bench line (extra args after ':', ',' for spaces) -> bench.json
-#   cfgs                the cfg2 / cfg4 / cfg5 bench lines              -> cfg{2,4,5}.json
+#   bench[:<args>]      the bench line with --full (extra args after ':', ',' for spaces) -> bench.json
+#   cfgs                the cfg2 / cfg4 / cfg5 bench lines with --full  -> cfg{2,4,5}.json
 #   profile             profiles/run_profile.sh (kernel trace + env PMC traffic of the bench)
 #   profile_cfg:<cfgs>  tools/profile_cfg.sh for the listed configs (',' separated)
 #   pmc[:<cfg>:<filter>] profiles/run_pmc.sh (PMC passes of the kernels matching filter)
@@ -44,10 +44,10 @@ for step in "$@"; do
     smoke)
       timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > "$O/smoke.log" 2>&1 || fail "$step" $? ;;
     bench)
-      timeout -k 10 400 python bench.py ${a1//,/ } > "$O/bench.json" 2> "$O/bench.err" || fail "$step" $? ;;
+      timeout -k 10 400 python bench.py --full ${a1//,/ } > "$O/bench.json" 2> "$O/bench.err" || fail "$step" $? ;;
     cfgs)
       for c in cfg2 cfg4 cfg5; do
-        timeout -k 10 300 python bench.py --config "$c" --no-cpu-baseline > "$O/$c.json" 2> "$O/$c.err" || fail "$step $c" $?
+        timeout -k 10 300 python bench.py --full --config "$c" --no-cpu-baseline > "$O/$c.json" 2> "$O/$c.err" || fail "$step $c" $?
       done ;;
     profile)
       bash profiles/run_profile.sh "$TAG" > "$O/profile.log" 2>&1 || fail "$step" $? ;;

@@ -10,7 +10,7 @@ mkdir -p "$O"
 export TMPDIR=/tmp
 for c in "${CFGS[@]}"; do
   cd "$R"
-  timeout -k 10 300 python bench.py --config "$c" --no-cpu-baseline > "$O/$c.json" 2> "$O/$c.err"
+  timeout -k 10 300 python bench.py --full --config "$c" --no-cpu-baseline > "$O/$c.json" 2> "$O/$c.err"
   cd /tmp
   timeout -k 10 300 rocprofv3 --kernel-trace --stats -f csv -d "$O/trace_$c" -o run -- \
     python3 "$R/bench.py" --config "$c" --steps 1 --warmup 1 --no-cpu-baseline > "$O/trace_$c.json" 2> "$O/trace_$c.err"
