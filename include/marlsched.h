@@ -17,6 +17,8 @@
  *   ms_env_randbelow <- random.randint/_randbelow on the env's global stream
  *                      (Agent.py:718,725; SchedulingEnvironment.py:317-326)
  *   ms_policy_act   <- PPO.selectAction / ActorCritic.act  PPOmodules.py:53-63,114-125
+ *   ms_policy_act_greedy, ms_act_round_greedy <- the same forward with torch.argmax for the sample
+ *                      (evaluating a trained policy; no counterpart in the reference's drivers)
  *   ms_discounted_returns, ms_unit_returns <- PPO.update return estimate  PPOmodules.py:128-137
  *
  * Conventions: plain pointers and sizes; every device pointer is a HIP device
@@ -36,7 +38,7 @@
 extern "C" {
 #endif
 
-#define MS_ABI_VERSION 18
+#define MS_ABI_VERSION 19
 
 #define MS_MAX_KINDS 16
 #define MS_MAX_AGENTS 64
@@ -386,6 +388,31 @@ int ms_act_round_free(const ms_mlp_params* core_chooser, const ms_mlp_params* pr
                       int8_t* core_action, float* core_logprob, int8_t* price_state, int8_t* price_action,
                       float* price_logprob, int8_t* env_price, int8_t* acc_action, float* acc_logprob,
                       const ms_price_table* price_table, int64_t price_unit_stride, void* stream);
+
+/* Greedy (deterministic) acting for policy evaluation (ABI 19): the argmax of ActorCritic.actor's logits
+ * (PPOmodules.py:53-63 without the Categorical sample), first maximum as torch.argmax takes it; rows,
+ * groups and weights as ms_policy_act. common_row (optional): rows equal to it take the group's
+ * common-row action, computed once (same outputs). logprob optional (NULL: not written), the chosen
+ * action's logit - logsumexp. No RNG is read or advanced; act_frag and row_base are ignored.
+ * MS_EINVAL for shapes outside hidden 16, A <= 127 and obs_stride <= 256. */
+int ms_policy_act_greedy(const ms_mlp_params* p, const int8_t* obs, int32_t obs_stride, int64_t n_envs,
+                         int32_t n_units, int32_t units_per_group, const int8_t* common_row,
+                         int8_t* action, float* logprob, void* stream);
+
+/* One round's getActionForAllAgents (SchedulingEnvironment.py:150-172), greedy, in one launch (two for shapes
+ * without a paired kernel), on the observations ms_env_step emits: offer rows + compact acceptor rows
+ * (core_rows / core_owner). price_chooser != NULL: FreePriceOfferPPO.selectAction (PPOmodules.py:312-332)
+ * with both picks greedy: price_state from the greedy core action a ([obs[2a], obs[2a+1], obs[2C], obs[2C+1]],
+ * or [-5,-5,-5,-5] when a == 0), env_price = -5 when a == 0 else the price action, laid out [E][U] as
+ * ms_offer_act_free lays them out. price_chooser == NULL: fixed prices, the price outputs NULL.
+ * Acceptor unit u = a*C + c acts on core row (e, c) when core_owner[e][c] == a + 1, else on common_row;
+ * outputs equal ms_policy_act_greedy on the regenerated [E][N*C] rows, bit for bit. */
+int ms_act_round_greedy(const ms_mlp_params* core_chooser, const ms_mlp_params* price_chooser,
+                        const int8_t* off_obs, int32_t off_stride, int32_t off_units, int32_t off_units_per_group,
+                        const ms_mlp_params* acceptor, const int8_t* core_rows, const int8_t* core_owner,
+                        int32_t acc_stride, int32_t acc_units, int32_t acc_units_per_group, int32_t n_cores,
+                        const int8_t* common_row, int64_t n_envs, int8_t* core_action, int8_t* price_state,
+                        int8_t* price_action, int8_t* env_price, int8_t* acc_action, void* stream);
 
 /* The next round's getActionForAllAgents fused into the env round (ABI 16; SchedulingEnvironment.py:
  * 150-172 with PPOmodules.py:53-63): after the round's observations, the wave that stepped a replica

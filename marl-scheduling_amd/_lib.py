@@ -27,7 +27,7 @@ class MarlSchedError(RuntimeError):
         self.code = code
 
 
-ABI_VERSION = 18  # include/marlsched.h MS_ABI_VERSION
+ABI_VERSION = 19  # include/marlsched.h MS_ABI_VERSION
 
 
 def _load():
@@ -79,6 +79,10 @@ def _load():
         "ms_act_round_free": (ct.c_int, [ct.POINTER(abi.MsMlpParams), ct.POINTER(abi.MsMlpParams), P, i32, i32, i32,
                                          ct.POINTER(abi.MsMlpParams), P, P, i32, i32, i32, i32, P, i64, u64, u64, u64,
                                          P, P, P, P, P, P, P, P, P, ct.POINTER(abi.MsPriceTable), i64, P]),
+        "ms_policy_act_greedy": (ct.c_int, [ct.POINTER(abi.MsMlpParams), P, i32, i64, i32, i32, P, P, P, P]),
+        "ms_act_round_greedy": (ct.c_int, [ct.POINTER(abi.MsMlpParams), ct.POINTER(abi.MsMlpParams), P, i32, i32, i32,
+                                           ct.POINTER(abi.MsMlpParams), P, P, i32, i32, i32, i32, P, i64, P, P, P, P, P,
+                                           P]),
         "ms_price_table_build": (ct.c_int, [ct.POINTER(abi.MsMlpParams), ct.POINTER(abi.MsPriceTable), P]),
         "ms_act_frag_bytes": (ct.c_size_t, [ct.POINTER(abi.MsMlpParams), i32]),
         "ms_act_prepare": (ct.c_int, [ct.POINTER(abi.MsMlpParams), P, i32, P, P]),
@@ -126,15 +130,17 @@ def _load():
     # ABI 14 added ms_bdqn_update*, 15 ms_bdqn_act_compact, 16 ms_mlp_params.row_base (a trailing field an
     # older library does not read: its acting draws are those of row_base 0) and ms_env_step_act /
     # ms_env_rollout_act, 17 ms_env_rollout_act_free, 18 its own_action / own_logprob (trailing fields a 17
-    # library does not read: it writes the owned items into the rings itself). An older library (an A/B variant built
-    # before them, tools/gpu_job.sh ab step) loads without them only when MARLSCHED_LENIENT_ABI=1 asks for it
-    lenient = os.environ.get("MARLSCHED_LENIENT_ABI") == "1" and version in (13, 14, 15, 16, 17, 18)
+    # library does not read: it writes the owned items into the rings itself), 19 the greedy acting entry points
+    # (ms_policy_act_greedy, ms_act_round_greedy). An older library (an A/B variant built before them,
+    # tools/gpu_job.sh ab step) loads without them only when MARLSCHED_LENIENT_ABI=1 asks for it
+    lenient = os.environ.get("MARLSCHED_LENIENT_ABI") == "1" and version in (13, 14, 15, 16, 17, 18, 19)
     if version != ABI_VERSION and not lenient:
         raise ImportError("libmarlsched.so ABI version mismatch (%d, want %d)" % (version, ABI_VERSION))
     for name, (res, args) in sig.items():
         if (version < 14 and name.startswith("ms_bdqn_update")) or (version < 15 and name == "ms_bdqn_act_compact") \
                 or (version < 16 and (name.startswith("ms_env_step_act") or name == "ms_env_rollout_act")) \
-                or (version < 17 and name.startswith("ms_env_rollout_act_free")):
+                or (version < 17 and name.startswith("ms_env_rollout_act_free")) \
+                or (version < 19 and name.endswith("_greedy")):
             continue
         if lenient and not hasattr(L, name):  # an older build of this ABI (A/B variants)
             continue
@@ -160,7 +166,7 @@ EXPORTED = (
     "ms_env_rollout_act_free", "ms_env_rollout_act_free_supported", "ms_env_rollout_fill_common", "ms_env_round", "ms_env_flags", "ms_env_randbelow", "ms_env_auctioneer",
     "ms_env_get_rng", "ms_env_set_rng", "ms_env_export",
     "ms_env_import", "ms_policy_act", "ms_policy_act_common", "ms_policy_act_compact",
-    "ms_act_round_free", "ms_price_table_build", "ms_act_frag_bytes", "ms_act_prepare", "ms_offer_act_free", "ms_discounted_returns", "ms_unit_returns",
+    "ms_act_round_free", "ms_policy_act_greedy", "ms_act_round_greedy", "ms_price_table_build", "ms_act_frag_bytes", "ms_act_prepare", "ms_offer_act_free", "ms_discounted_returns", "ms_unit_returns",
     "ms_ppo_workspace_bytes", "ms_ppo_grad", "ms_adam_step", "ms_adam_step_dev",
     "ms_aggregate_obs", "ms_decode_aggregated", "ms_dqn_act", "ms_dqn_workspace_bytes", "ms_dqn_grad",
     "ms_regen_agent_rows", "ms_bdqn_workspace_bytes", "ms_bdqn_prepare", "ms_bdqn_layer1_scratch_bytes", "ms_bdqn_layer1_compact",

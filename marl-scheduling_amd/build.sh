@@ -17,12 +17,12 @@ HEADERS=("${HERE}/csrc/ms_layout.h" "${HERE}/csrc/ms_act.h" "${HERE}/csrc/ms_ppo
 CCVER="$("${HIPCC}" --version 2>/dev/null | head -3 | tr '\n' ' ')"
 objs=()
 pids=()
-for src in env_kernels.hip policy_kernels.hip act_pair_kernels.hip returns_kernels.hip ppo_kernels.hip agg_kernels.hip dqn_kernels.hip bdqn_kernels.hip bdqn_update_kernels.hip wide_kernels.hip capi.cpp; do
+for src in env_kernels.hip policy_kernels.hip act_pair_kernels.hip greedy_kernels.hip returns_kernels.hip ppo_kernels.hip agg_kernels.hip dqn_kernels.hip bdqn_kernels.hip bdqn_update_kernels.hip wide_kernels.hip capi.cpp; do
   obj="${OBJDIR}/${src%.*}.o"
   # the env round reproduces Python's float64 arithmetic: no contraction there; the policy
   # and PPO kernels follow torch's f32 (which fuses freely) within tolerance: fma allowed
   contract=(-ffp-contract=off)
-  [[ "${src}" == policy_kernels.hip || "${src}" == act_pair_kernels.hip || "${src}" == returns_kernels.hip ]] && contract=(-ffp-contract=fast)
+  [[ "${src}" == policy_kernels.hip || "${src}" == act_pair_kernels.hip || "${src}" == greedy_kernels.hip || "${src}" == returns_kernels.hip ]] && contract=(-ffp-contract=fast)
   # the gradient kernel's variants (common rows by bytes or by owners) must agree bit for bit: fma only
   # where an expression asks for it, never across statements (fast contraction depends on the code around)
   [[ "${src}" == ppo_kernels.hip || "${src}" == bdqn_kernels.hip || "${src}" == wide_kernels.hip ]] && contract=(-ffp-contract=on)

@@ -46,6 +46,11 @@ hipError_t launch_act_round(const ms_mlp_params*, const ms_mlp_params*, const in
                             const ms_mlp_params*, const int8_t*, const int8_t*, int, int, int, int, const int8_t*,
                             int64_t, uint64_t, uint64_t, uint64_t, const uint64_t*, int8_t*, float*, int8_t*, int8_t*,
                             float*, int8_t*, int8_t*, float*, const float*, const int16_t*, int, int64_t, hipStream_t);
+hipError_t launch_policy_act_greedy(const ms_mlp_params*, const int8_t*, int, int64_t, int, int, const int8_t*, int8_t*,
+                                    float*, hipStream_t);
+hipError_t launch_act_round_greedy(const ms_mlp_params*, const ms_mlp_params*, const int8_t*, int, int, int,
+                                   const ms_mlp_params*, const int8_t*, const int8_t*, int, int, int, int,
+                                   const int8_t*, int64_t, int8_t*, int8_t*, int8_t*, int8_t*, int8_t*, hipStream_t);
 hipError_t launch_price_table(const ms_mlp_params*, const int8_t*, int, float*, hipStream_t);
 size_t act_frag_bytes(const ms_mlp_params*, int);
 hipError_t launch_act_prepare(const ms_mlp_params*, const int8_t*, int, void*, hipStream_t);
@@ -775,6 +780,59 @@ int ms_act_round_free(const ms_mlp_params* core, const ms_mlp_params* price, con
                                  price_table ? price_table->table : nullptr, price_table ? price_table->digit : nullptr,
                                  price_table ? price_table->n_keys : 0, price_unit_stride, (hipStream_t)stream));
     return MS_OK;
+}
+
+// a greedy launch the kernels are not built for (greedy_kernels.hip reports it before launching anything)
+static int greedy_rc(hipError_t e, const char* who) {
+    if (e == hipSuccess) return MS_OK;
+    if (e == hipErrorInvalidValue) return fail(MS_EINVAL, "%s: shape not built (hidden 16, A <= 127, stride <= 256)", who);
+    return fail(MS_EHIP, "%s: %s", who, hipGetErrorString(e));
+}
+
+int ms_policy_act_greedy(const ms_mlp_params* p, const int8_t* obs, int32_t obs_stride, int64_t n_envs, int32_t n_units,
+                         int32_t units_per_group, const int8_t* common_row, int8_t* action, float* logprob,
+                         void* stream) {
+    if (!obs || !action) return fail(MS_EINVAL, "NULL argument");  // (logprob and common_row are optional)
+    int rc = check_mlp(p, obs_stride, n_units, units_per_group);
+    if (rc) return rc;
+    if (n_envs < 1) return fail(MS_EINVAL, "n_envs must be >= 1");
+    return greedy_rc(ms::launch_policy_act_greedy(p, obs, obs_stride, n_envs, n_units, units_per_group, common_row,
+                                                  action, logprob, (hipStream_t)stream),
+                     "ms_policy_act_greedy");
+}
+
+int ms_act_round_greedy(const ms_mlp_params* core, const ms_mlp_params* price, const int8_t* off_obs, int32_t off_stride,
+                        int32_t off_units, int32_t off_units_per_group, const ms_mlp_params* acc,
+                        const int8_t* core_rows, const int8_t* core_owner, int32_t acc_stride, int32_t acc_units,
+                        int32_t acc_units_per_group, int32_t n_cores, const int8_t* common_row, int64_t n_envs,
+                        int8_t* core_action, int8_t* price_state, int8_t* price_action, int8_t* env_price,
+                        int8_t* acc_action, void* stream) {
+    if (!off_obs || !core_rows || !core_owner || !common_row || !core_action || !acc_action)
+        return fail(MS_EINVAL, "NULL argument");
+    // price == NULL: a fixed-price round (the offer units' net acts alone; no price outputs)
+    if (price && (!price_state || !price_action || !env_price)) return fail(MS_EINVAL, "NULL price output");
+    if (!price && (price_state || price_action || env_price))
+        return fail(MS_EINVAL, "a fixed-price round (price_chooser NULL) takes no price outputs");
+    if (n_envs < 1) return fail(MS_EINVAL, "n_envs must be >= 1");
+    int rc = check_mlp(core, off_stride, off_units, off_units_per_group);
+    if (rc) return rc;
+    if (price) {
+        rc = check_mlp(price, 4, off_units, off_units_per_group);
+        if (rc) return rc;
+    }
+    rc = check_mlp(acc, acc_stride, acc_units, acc_units_per_group);
+    if (rc) return rc;
+    if (price && (price->in_dim != 4 || price->n_groups != core->n_groups))
+        return fail(MS_EINVAL, "price chooser must be 4 -> A");
+    if (core->in_dim != 2 * n_cores + 2 || core->n_actions != n_cores + 1)
+        return fail(MS_EINVAL, "core chooser must be (2C+2) -> C+1");
+    if (n_cores < 1 || acc_units % n_cores != 0)
+        return fail(MS_EINVAL, "acceptor units must be n_agents * n_cores");
+    return greedy_rc(ms::launch_act_round_greedy(core, price, off_obs, off_stride, off_units, off_units_per_group, acc,
+                                                 core_rows, core_owner, acc_stride, acc_units, acc_units_per_group,
+                                                 n_cores, common_row, n_envs, core_action, price_state, price_action,
+                                                 env_price, acc_action, (hipStream_t)stream),
+                     "ms_act_round_greedy");
 }
 
 int ms_price_table_build(const ms_mlp_params* price_chooser, const ms_price_table* t, void* stream) {

@@ -194,6 +194,28 @@ class GroupedActorCritic(nn.Module):
                                         ptr(offset_dev), ptr(uniforms), ptr(action), ptr(logprob), stream_ptr(stream)))
         return action, logprob
 
+    @torch.no_grad()
+    def act_greedy(self, obs_i8, n_units: int, common_row=None, action=None, logprob=None, stream=None):
+        """The deterministic counterpart of ``act`` for evaluating a policy (ms_policy_act_greedy): the
+        first maximum of the actor's logits (torch.argmax's rule) for obs [E, n_units, stride] int8, and
+        the chosen action's log-prob (log_softmax). No random number is drawn. common_row (optional): rows
+        equal to it take the group's common-row action, computed once (same outputs).
+        Returns (action int8 [E, U], logprob f32 [E, U])."""
+        E, U, stride = obs_i8.shape
+        assert U == n_units and U % self.G == 0 and obs_i8.dtype == torch.int8 and obs_i8.is_contiguous()
+        dev = obs_i8.device
+        if action is None:
+            action = torch.empty((E, U), dtype=torch.int8, device=dev)
+        if logprob is None:
+            logprob = torch.empty((E, U), dtype=torch.float32, device=dev)
+        assert action.is_contiguous() and logprob.is_contiguous() and action.numel() == logprob.numel() == E * U
+        if common_row is not None:
+            assert common_row.dtype == torch.int8 and common_row.numel() == stride and common_row.device == dev
+        p = self.mlp_params()
+        check(lib.ms_policy_act_greedy(ct.byref(p), ptr(obs_i8), stride, E, U, U // self.G, ptr(common_row),
+                                       ptr(action), ptr(logprob), stream_ptr(stream)))
+        return action, logprob
+
 
 class PriceTable:
     """The price chooser's sampling table (ms_price_table): the inputs the env can hand it are
@@ -281,6 +303,34 @@ def act_round_free(core: GroupedActorCritic, price: GroupedActorCritic, off_obs,
                                 ptr(out["core_logprob"]), *[ptr(x) for x in prices], ptr(acc_action), ptr(acc_logprob),
                                 ct.byref(price_table.struct) if price_table is not None else None,
                                 int(price_unit_stride), stream_ptr(stream)))
+
+
+@torch.no_grad()
+def act_round_greedy(core: GroupedActorCritic, price: GroupedActorCritic | None, off_obs, acc: GroupedActorCritic,
+                     core_rows, core_owner, common_row, n_cores: int, out: dict, acc_action, stream=None):
+    """One round's getActionForAllAgents (SchedulingEnvironment.py:150-172) with every pick greedy
+    (ms_act_round_greedy), on the observations the env emits: the offer rows and the compact acceptor rows.
+    Arguments as ``act_round_free`` without seeds, offsets and log-probs: out holds core_action [E, U] and,
+    with a price chooser, price_state [E, U, 4], price_action and env_price [E, U] (int8); price None: a
+    fixed-price round. acc_action [E, N*C] equals ``acc.act_greedy`` on the regenerated rows."""
+    E, U_off, off_stride = off_obs.shape
+    _, C, acc_stride = core_rows.shape
+    U_acc = acc_action.shape[1]
+    assert off_obs.is_contiguous() and core_rows.is_contiguous() and core_owner.is_contiguous()
+    assert core_owner.shape == (E, C) and acc_action.is_contiguous() and acc_action.shape == (E, U_acc)
+    assert out["core_action"].is_contiguous() and out["core_action"].shape == (E, U_off)
+    pc, pa = core.mlp_params(), acc.mlp_params()
+    if price is None:
+        pp, prices = None, (None, None, None)
+    else:
+        _check_price_out(dict(out, price_logprob=out["price_action"]), E, U_off, 0)
+        assert out["env_price"].is_contiguous() and out["env_price"].shape == (E, U_off)
+        pp = ct.byref(price.mlp_params())
+        prices = (out["price_state"], out["price_action"], out["env_price"])
+    check(lib.ms_act_round_greedy(ct.byref(pc), pp, ptr(off_obs), off_stride, U_off, U_off // core.G, ct.byref(pa),
+                                  ptr(core_rows), ptr(core_owner), acc_stride, U_acc, U_acc // acc.G, n_cores,
+                                  ptr(common_row), E, ptr(out["core_action"]), *[ptr(x) for x in prices],
+                                  ptr(acc_action), stream_ptr(stream)))
 
 
 def _check_price_out(out, E: int, U: int, pus: int):

@@ -32,8 +32,8 @@ import torch
 from . import abi
 from ._lib import ABI_LOADED, hip_capture, ptr
 from .env import BatchedEnv
-from .ppo import (ActFrag, PPOGroup, PriceTable, act_round_free, combine_losses, discounted_returns, offer_act_free,
-                  reference_init_order, reference_nets, unit_returns)
+from .ppo import (ActFrag, PPOGroup, PriceTable, act_round_free, act_round_greedy, combine_losses, discounted_returns,
+                  offer_act_free, reference_init_order, reference_nets, unit_returns)
 
 
 @dataclass
@@ -914,6 +914,140 @@ class Trainer:
                 b[slot].zero_()
             self.episode_log.append(mx.episode_values(mx.view(raw), self.cfg, self.ep_len, s.n_agents, s.n_cores,
                                                       s.collection_length))
+
+    # ---- evaluation
+    def eval_seed(self, n_envs: int | None = None) -> int:
+        """Default base seed of evaluate()'s replicas: the training env's base seed of this rank (env_seed)
+        plus 500_001, half the distance between two trainer seeds' ranges, so the evaluation replicas
+        [base, base + n_envs) meet no training replica's job stream while world_size * E < 500_001."""
+        return env_seed(self.seed, self.rank, int(n_envs or self.E)) + 500_001
+
+    def _eval_buffers(self, E: int):
+        """evaluate()'s observation / action / reward tensors for E replicas (kept between calls)."""
+        cache = self.__dict__.setdefault("_eval_cache", {})
+        if E not in cache:
+            s, dev, i8 = self.env.shape, self.device, torch.int8
+            N, C, L = self.N, self.C, self.L
+            z = lambda *shape, dtype=i8: torch.zeros(shape, dtype=dtype, device=dev)
+            b = dict(offer=z(E, N * L, s.off_obs_stride), acc_action=z(E, N * C), off_action=z(E, N * L),
+                     acc_logprob=z(E, N * C, dtype=torch.float32), off_logprob=z(E, N * L, dtype=torch.float32))
+            if self.compact:
+                b.update(core_rows=z(E, C, s.acc_obs_stride), core_owner=z(E, C))
+            else:
+                b.update(acceptor=z(E, N * C, s.acc_obs_stride))
+            if self.free:
+                b.update(price_state=z(E, N * L, 4), price_action=z(E, N * L), env_price=z(E, N * L),
+                         price_logprob=z(E, N * L, dtype=torch.float32))
+            b["rewards"] = dict(offer=z(E, N, L, dtype=torch.float32), acceptor=z(E, N, C, dtype=torch.int32),
+                                agent=z(E, N, dtype=torch.int32), auctioneer=z(E, C, dtype=torch.int32),
+                                price=z(E, N, L, dtype=torch.float32) if self.free else None)
+            cache[E] = b
+        return cache[E]
+
+    def _eval_act(self, b: dict, mode: str, t: int, philox_seed: int):
+        """getActionForAllAgents of evaluation round t on the observations in b, with policy_old (the nets the
+        next rollout acts with): greedy (argmax) or sampled picks, into b's action tensors."""
+        N, C, L = self.N, self.C, self.L
+        off, acc = self.off.group.policy_old, self.acc.group.policy_old
+        price = self.price.group.policy_old if self.free else None
+        if mode == "greedy":
+            if self.compact:
+                out = dict(core_action=b["off_action"])
+                if self.free:
+                    out.update(price_state=b["price_state"], price_action=b["price_action"], env_price=b["env_price"])
+                act_round_greedy(off, price, b["offer"], acc, b["core_rows"], b["core_owner"], self.acc_common, C,
+                                 out, b["acc_action"])
+                return
+            off.act_greedy(b["offer"], N * L, action=b["off_action"], logprob=b["off_logprob"])
+            if self.free:
+                # FreePriceOfferPPO.selectAction (PPOmodules.py:312-332) on the greedy core action a:
+                # [obs[2a], obs[2a+1], obs[2C], obs[2C+1]], or the dummy [-5, -5, -5, -5] when a == 0
+                a = b["off_action"].long()
+                idx = torch.stack([2 * a, 2 * a + 1, torch.full_like(a, 2 * C), torch.full_like(a, 2 * C + 1)], -1)
+                st = torch.gather(b["offer"], 2, idx)
+                b["price_state"].copy_(torch.where((a == 0).unsqueeze(-1), torch.full_like(st, -5), st))
+                price.act_greedy(b["price_state"], N * L, action=b["price_action"], logprob=b["price_logprob"])
+                b["env_price"].copy_(torch.where(a == 0, torch.full_like(b["price_action"], -5), b["price_action"]))
+            acc.act_greedy(b["acceptor"], N * C, action=b["acc_action"], logprob=b["acc_logprob"])
+            return
+        # sampled picks: the training calls with the rounds' static Philox offsets (_act_part), no device counter
+        base = 8 * t
+        out = dict(core_action=b["off_action"], core_logprob=b["off_logprob"])
+        if self.free:
+            out.update(price_state=b["price_state"], price_action=b["price_action"],
+                       price_logprob=b["price_logprob"], env_price=b["env_price"])
+        if self.compact:
+            act_round_free(off, price, b["offer"], acc, b["core_rows"], b["core_owner"], self.acc_common, C,
+                           philox_seed, base + 1, base + 3, out, b["acc_action"], b["acc_logprob"])
+            return
+        if self.free:
+            offer_act_free(off, price, b["offer"], C, philox_seed, base + 1, out)
+        else:
+            off.act(b["offer"], N * L, philox_seed, base + 1, action=b["off_action"], logprob=b["off_logprob"])
+        acc.act(b["acceptor"], N * C, philox_seed, base + 3, action=b["acc_action"], logprob=b["acc_logprob"],
+                common_row=self.acc_common if self.common_rows else None)
+
+    @torch.no_grad()
+    def evaluate(self, episodes: int = 1, n_envs: int | None = None, mode: str = "greedy", seed: int | None = None,
+                 trace: bool = False) -> dict:
+        """Evaluate the current policy (policy_old, the nets the next rollout acts with) for `episodes` episodes
+        of episode_length rounds on n_envs (default: E) fresh replicas of their own; replica e is seeded
+        seed + e (default seed: eval_seed()). Training state is left untouched: the training env, the rings,
+        the sub-unit and Philox counters, the episode log and the captured graphs are neither read nor written.
+
+        mode "greedy": every unit takes the argmax of its actor's logits (no random number drawn);
+        mode "sample": the units sample as in training, Philox key from `seed`;
+        mode "hardcoded": the in-kernel HardcodedOfferer / HardcodedAcceptor agents, the reference's baseline
+        (fixed prices only: ValueError under free prices).
+
+        Eager launches on the current stream (one act launch and one env round per round). Each call steps a
+        newly created env (an env's reset re-emits observations; it does not rewind the world or its job
+        stream), so equal arguments give equal results; the tensors are kept between calls, and the last env
+        as self.eval_env. Several ranks: each evaluates its own replicas, no collective.
+        Returns dict(mode, seed, n_envs, episodes=[metrics.reduce_replicas(ep), ...] (the argsDict values
+        Plot.py reads, averaged over replicas), per_replica=[[dict per replica] per episode]); with trace also
+        trace=[per round: the observations acted on and every action array fed to the env, CPU tensors]."""
+        from . import metrics as mx
+        if mode not in ("greedy", "sample", "hardcoded"):
+            raise ValueError("mode must be 'greedy', 'sample' or 'hardcoded'")
+        if mode == "hardcoded" and self.free:
+            raise ValueError("the hard-coded agents act under fixed prices only")
+        episodes, E = int(episodes), int(n_envs or self.E)
+        if episodes < 1 or E < 1:
+            raise ValueError("episodes and n_envs must be >= 1")
+        seed = self.eval_seed(E) if seed is None else int(seed)
+        N, C, L = self.N, self.C, self.L
+        b = self._eval_buffers(E)
+        env = self.eval_env = BatchedEnv(self.cfg, E, seed=seed, device=self.device)
+        obs_keys = ("core_rows", "core_owner", "offer") if self.compact else ("acceptor", "offer")
+        obs = {k: b[k] for k in obs_keys}
+        env.reset(obs)
+        mbuf = env.metrics_buffer(episodes)  # round r adds into slot (r // episode_length) % episodes
+        philox_seed = (seed * 7919) & 0xFFFFFFFFFFFFFFFF
+        rounds = []
+        for t in range(episodes * self.ep_len):
+            if mode == "hardcoded":
+                acts = (None, None, None)
+            else:
+                self._eval_act(b, mode, t, philox_seed)
+                acts = (b["acc_action"].view(E, N, C), b["off_action"].view(E, N, L),
+                        b["env_price"].view(E, N, L) if self.free else None)
+            if trace:
+                rec = {k: b[k].cpu() for k in obs_keys}
+                if mode != "hardcoded":
+                    rec.update(acceptor_action=b["acc_action"].cpu(), offer_action=b["off_action"].cpu())
+                    if self.free:
+                        rec.update(price_state=b["price_state"].cpu(), price_action=b["price_action"].cpu(),
+                                   offer_price=b["env_price"].cpu())
+                rounds.append(rec)
+            env.step(*acts, obs=obs, rewards=b["rewards"], events=dict(metrics=mbuf))
+        raw = mbuf.cpu().numpy()
+        per_replica = [mx.episode_values(mx.view(raw[k]), self.cfg, self.ep_len, N, C, L) for k in range(episodes)]
+        res = dict(mode=mode, seed=seed, n_envs=E, episodes=[mx.reduce_replicas(ep) for ep in per_replica],
+                   per_replica=per_replica)
+        if trace:
+            res["trace"] = rounds
+        return res
 
     def args_dict(self, replica="mean", params=None):
         """argsDict of the finished episodes (trainPPO.py:229-243): replica = "mean" averages the

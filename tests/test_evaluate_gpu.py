@@ -1,0 +1,204 @@
+"""Trainer.evaluate: deterministic (greedy), sampled and hard-coded evaluation of the current policy on an
+env of its own. The traced picks against a float64 restatement, the metrics against a replay of the traced
+actions, and training left exactly as it was."""
+import importlib
+
+import numpy as np
+import pytest
+import torch
+
+from tests.test_greedy_gpu import _cpu_weights, _logits, check_greedy_rows
+
+pytestmark = pytest.mark.gpu
+
+E, T, EP = 16, 8, 8  # replicas, update_step, episode_length
+
+
+def _mods():
+    return (importlib.import_module("marl-scheduling_amd.trainer"), importlib.import_module("marl-scheduling_amd.ppo"),
+            importlib.import_module("marl-scheduling_amd.metrics"))
+
+
+def _trainer(name, seed=3, **kw):
+    tr = _mods()[0]
+    return tr.Trainer.from_named(name, n_envs=E, update_step=T, seed=seed, device="cuda:0", episode_length=EP, **kw)
+
+
+def _same(a, b):
+    """Exact equality of evaluate()'s nested results (dicts, lists, arrays, floats, None)."""
+    if isinstance(a, dict):
+        return isinstance(b, dict) and a.keys() == b.keys() and all(_same(a[k], b[k]) for k in a)
+    if isinstance(a, (list, tuple)):
+        return len(a) == len(b) and all(_same(x, y) for x, y in zip(a, b))
+    if isinstance(a, torch.Tensor):
+        return torch.equal(a, b)
+    if isinstance(a, np.ndarray):
+        return np.array_equal(a, b)
+    return a == b
+
+
+def _check_unit(ppo, net, rows, actions, what):
+    """rows [R, U, stride] int8 (CPU), actions [R, U]: every pick is the float64 argmax of its group's logits,
+    within the near-tie allowance."""
+    w = _cpu_weights(ppo, net)
+    U, S = rows.shape[1], rows.shape[1] // net.G
+    l64, l32, act = [], [], []
+    for g in range(net.G):
+        x = rows[:, g * S:(g + 1) * S, :net.D].reshape(-1, net.D)
+        l64.append(_logits(w, g, x, torch.float64))
+        l32.append(_logits(w, g, x, torch.float32))
+        act.append(actions[:, g * S:(g + 1) * S].reshape(-1).long())
+    check_greedy_rows(torch.cat(act), torch.cat(l64), torch.cat(l32), what, max_near=None)
+
+
+@pytest.mark.parametrize("name", ["cfg1", "cfg2", "cfg3"])
+def test_greedy_trace_consistent(ms, name):
+    tr, ppo, mx = _mods()
+    t = _trainer(name)
+    N, C, L = t.N, t.C, t.L
+    assert t.compact == (name != "cfg1")
+    res = t.evaluate(episodes=2, n_envs=E, mode="greedy", seed=123, trace=True)
+    assert (res["mode"], res["seed"], res["n_envs"]) == ("greedy", 123, E)
+    trace = res["trace"]
+    assert len(trace) == 2 * EP and len(res["episodes"]) == 2 and len(res["per_replica"][0]) == E
+    assert t.eval_env.flags() == 0
+    # every pick is the argmax of the observation it was made on
+    cat = lambda k: torch.cat([r[k] for r in trace])
+    off_obs, off_act = cat("offer").view(-1, N * L, t.off.stride), cat("offer_action")
+    if t.compact:
+        acc_rows = ppo.regen_acceptor_rows(cat("core_rows"), cat("core_owner"), t.acc_common.cpu(), N)
+    else:
+        acc_rows = cat("acceptor").view(-1, N * C, t.acc.stride)
+    _check_unit(ppo, t.acc.group.policy_old, acc_rows, cat("acceptor_action"), name + " acceptor:")
+    _check_unit(ppo, t.off.group.policy_old, off_obs, off_act, name + " offer:")
+    if t.free:
+        a = off_act.long()
+        idx = torch.stack([2 * a, 2 * a + 1, torch.full_like(a, 2 * C), torch.full_like(a, 2 * C + 1)], -1)
+        st = torch.gather(off_obs, 2, idx)
+        st[a == 0] = -5
+        assert torch.equal(cat("price_state"), st)
+        _check_unit(ppo, t.price.group.policy_old, st, cat("price_action"), name + " price:")
+        pa = cat("price_action")
+        assert torch.equal(cat("offer_price"), torch.where(a == 0, torch.full_like(pa, -5), pa))
+    # the metrics are those of the traced actions: replay them through a second env of the same seed
+    env = ms.BatchedEnv(t.cfg, E, seed=123)
+    mbuf = env.metrics_buffer(2)
+    obs = env.compact_obs_buffers() if t.compact else env.obs_buffers()
+    env.reset(obs)
+    for r in trace:
+        assert torch.equal(obs["offer"].cpu().view(r["offer"].shape), r["offer"])
+        price = r["offer_price"].cuda().view(E, N, L) if t.free else None
+        env.step(r["acceptor_action"].cuda().view(E, N, C), r["offer_action"].cuda().view(E, N, L), price, obs=obs,
+                 events=dict(metrics=mbuf))
+    raw = mbuf.cpu().numpy()
+    replay = [mx.episode_values(mx.view(raw[k]), t.cfg, EP, N, C, L) for k in range(2)]
+    assert _same(replay, res["per_replica"])
+    assert all(d["rounds"] == EP for ep in replay for d in ep)
+    assert _same(res["episodes"], [mx.reduce_replicas(ep) for ep in replay])
+    assert env.flags() == 0
+    # the same seed again: the same result; another seed: another trace
+    again = t.evaluate(episodes=2, n_envs=E, mode="greedy", seed=123, trace=True)
+    assert _same(again, res)
+    other = t.evaluate(episodes=2, n_envs=E, mode="greedy", seed=124, trace=True)
+    assert not _same(other["trace"], trace)
+    # the default seed is not the training env's
+    dflt = t.evaluate(episodes=1)
+    assert dflt["seed"] == t.eval_seed() and dflt["n_envs"] == E
+    assert not (tr.env_seed(t.seed, 0, E) <= dflt["seed"] < tr.env_seed(t.seed, 0, E) + E)
+
+
+def _training_state(t, losses):
+    """Everything two iterations leave behind that an evaluation in between must not change."""
+    st = {}
+    for u in t.units():
+        g = u.group
+        for pol_name, pol in (("policy", g.policy), ("policy_old", g.policy_old)):
+            for k, p in pol.named_parameters():
+                st["%s.%s.%s" % (u.name, pol_name, k)] = p.detach().clone()
+        for i, (p, s) in enumerate(g.hip_optimizer.state.items()):
+            st["%s.adam%d.m" % (u.name, i)] = s["exp_avg"].clone()
+            st["%s.adam%d.v" % (u.name, i)] = s["exp_avg_sq"].clone()
+        st[u.name + ".adam.step"] = (g.hip_optimizer.step_count, int(g.hip_optimizer.step_dev))
+        st[u.name + ".actions"] = u.actions.clone()
+        st[u.name + ".logprobs"] = u.logprobs.clone()
+        st[u.name + ".rewards"] = u.rewards.clone()
+    st["off_obs"] = t.off_obs.clone()
+    if t.compact:
+        st["acc_rows"], st["acc_owner"] = t.acc_rows.clone(), t.acc_owner.clone()
+    else:
+        st["acc_obs"] = t.acc_obs.clone()
+    if t.free:
+        st["price_obs"] = t.price_obs.clone()
+    st["rng_ctr"] = t.rng_ctr.clone()
+    st["rng"] = t.rng.getstate()
+    st["rounds_done"] = t.rounds_done
+    st["env_round"] = t.env.round
+    st["episode_log"] = len(t.episode_log)
+    for i, ls in enumerate(losses):
+        for k, v in ls.items():
+            st["loss%d.%s" % (i, k)] = v.clone()
+    return st
+
+
+_PLAIN = {}
+
+
+def _plain_run(name):
+    """Two iterations without an evaluation (once per config)."""
+    if name not in _PLAIN:
+        t = _trainer(name)
+        _PLAIN[name] = _training_state(t, [t.iteration(), t.iteration()])
+    return _PLAIN[name]
+
+
+@pytest.mark.parametrize("name,mode", [("cfg2", "greedy"), ("cfg2", "sample"), ("cfg2", "hardcoded"),
+                                       ("cfg3", "greedy"), ("cfg3", "sample")])
+def test_evaluate_leaves_training_untouched(ms, name, mode):
+    t = _trainer(name)
+    assert t.fused_rollout if name == "cfg2" else t.fused_rollout_free  # the one-launch rollouts
+    l1 = t.iteration()
+    version, acting = t._policy_version, t._acting_version
+    res = t.evaluate(episodes=1, mode=mode)
+    assert len(res["episodes"]) == 1 and t.eval_env.flags() == 0
+    assert (t._policy_version, t._acting_version) == (version, acting)
+    l2 = t.iteration()
+    got, want = _training_state(t, [l1, l2]), _plain_run(name)
+    assert got.keys() == want.keys()
+    for k in want:
+        assert _same(got[k], want[k]), k
+
+
+def test_hardcoded_baseline(ms):
+    """mode="hardcoded" is a bare env of that seed stepped by its in-kernel rule-based agents."""
+    mx = _mods()[2]
+    t = _trainer("cfg2")
+    s = 77
+    res = t.evaluate(episodes=2, mode="hardcoded", seed=s)
+    env = ms.BatchedEnv(t.cfg, E, seed=s)
+    mbuf = env.metrics_buffer(2)
+    obs = env.obs_buffers()
+    for _ in range(2 * EP):
+        env.step(None, None, obs=obs, events=dict(metrics=mbuf))
+    raw = mbuf.cpu().numpy()
+    want = [mx.episode_values(mx.view(raw[k]), t.cfg, EP, t.N, t.C, t.L) for k in range(2)]
+    assert _same(res["per_replica"], want)
+    assert res["mode"] == "hardcoded" and t.eval_env.flags() == 0
+    with pytest.raises(ValueError):
+        _trainer("cfg3").evaluate(mode="hardcoded")
+    with pytest.raises(ValueError):
+        t.evaluate(mode="best")
+
+
+@pytest.mark.parametrize("name", ["cfg1", "cfg2", "cfg3"])
+def test_sample_mode_reproducible(ms, name):
+    t = _trainer(name)
+    a = t.evaluate(episodes=1, mode="sample", seed=5, trace=True)
+    assert t.eval_env.flags() == 0
+    b = t.evaluate(episodes=1, mode="sample", seed=5, trace=True)
+    assert _same(a, b)
+    c = t.evaluate(episodes=1, mode="sample", seed=6, trace=True)
+    assert not _same(c["trace"], a["trace"])
+    g = t.evaluate(episodes=1, mode="greedy", seed=5, trace=True)
+    assert t.eval_env.flags() == 0
+    # sampling explores: the same world, other picks than the argmax somewhere in the episode
+    assert not _same([r["offer_action"] for r in g["trace"]], [r["offer_action"] for r in a["trace"]])
