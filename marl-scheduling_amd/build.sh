@@ -13,7 +13,7 @@ FLAGS=(-O3 -std=c++17 -fPIC --offload-arch="${ARCH}" -Wall -Wno-unused-function
 OBJDIR="${MS_OBJDIR:-${HERE}/build}"
 [[ "${MS_CLEAN:-0}" == 1 ]] && rm -rf "${OBJDIR}"
 mkdir -p "${OBJDIR}"
-HEADERS=("${HERE}/csrc/ms_layout.h" "${HERE}/csrc/ms_act.h" "${HERE}/csrc/ms_ppo.h" "${HERE}/csrc/ms_dqn.h" "${HERE}/csrc/ms_bdqn.h" "${HERE}/csrc/ms_wide.h" "${HERE}/csrc/ms_common.h" "${HERE}/../include/marlsched.h")
+HEADERS=("${HERE}/csrc/ms_layout.h" "${HERE}/csrc/ms_act.h" "${HERE}/csrc/ms_act_kernels.h" "${HERE}/csrc/ms_ppo.h" "${HERE}/csrc/ms_dqn.h" "${HERE}/csrc/ms_bdqn.h" "${HERE}/csrc/ms_wide.h" "${HERE}/csrc/ms_common.h" "${HERE}/../include/marlsched.h")
 CCVER="$("${HIPCC}" --version 2>/dev/null | head -3 | tr '\n' ' ')"
 objs=()
 pids=()
@@ -28,12 +28,10 @@ for src in env_kernels.hip policy_kernels.hip act_pair_kernels.hip greedy_kernel
   [[ "${src}" == ppo_kernels.hip || "${src}" == bdqn_kernels.hip || "${src}" == wide_kernels.hip ]] && contract=(-ffp-contract=on)
   # cfg3's paired acting kernel is a latency-bound chain: the ILP-first machine scheduler shortens it
   # (rollout 12.14 -> 11.88 ms, profiles/r3f2/ab_sched_ilp_act.txt); the env round gains nothing, and the
-  # gradient, returns and cfg4 acting kernels lose with it, so they keep the default (act_pair_kernels.hip)
-  [[ "${src}" == policy_kernels.hip ]] && contract+=(-DMS_SPLIT_PAIR)
+  # gradient, returns and the other acting kernels (k_act / k_act_common, cfg4) lose with it, so they keep the
+  # default; each acting kernel is defined in one unit only (ms_act_kernels.h holds what the units share)
   [[ "${src}" == act_pair_kernels.hip && "${MS_NO_ILP:-0}" != 1 ]] && contract+=(-mllvm -amdgpu-sched-strategy=max-ilp)
-  inc=()
-  [[ "${src}" == act_pair_kernels.hip ]] && inc=("${HERE}/csrc/policy_kernels.hip")  # it includes that file
-  key="$( { cat "${HERE}/csrc/${src}" "${inc[@]}" "${HEADERS[@]}"; echo "${CCVER} ${FLAGS[*]} ${contract[*]}"; } | sha256sum | cut -d' ' -f1)"
+  key="$( { cat "${HERE}/csrc/${src}" "${HEADERS[@]}"; echo "${CCVER} ${FLAGS[*]} ${contract[*]}"; } | sha256sum | cut -d' ' -f1)"
   if [[ ! -f "${obj}" || "$(cat "${obj}.key" 2>/dev/null)" != "${key}" ]]; then
     rm -f "${obj}.key"
     lang=()

@@ -21,8 +21,7 @@
 #include <math.h>
 
 #include "../../include/marlsched.h"
-#include "ms_common.h"
-#include "ms_act.h"
+#include "ms_act_kernels.h"  // the launch-shape helpers shared with the sampling kernels
 
 #pragma clang fp contract(fast)  // (build.sh: -ffp-contract=fast for this file)
 
@@ -45,27 +44,11 @@ struct GreedyArgs {
 
 constexpr int kGreedySeg = 512;  // most items per wave of k_greedy_common = capacity of its LDS row list
 
-// the logits of the tile's 16 rows from their layer-1 pre-activations: z[t][q] = logit of action
-// a = 16 t + 4 g4 + q of row j, -inf for the padding actions a >= A (Head::numerators' layers 2-3)
+// the logits of the tile's 16 rows from their layer-1 pre-activations (Head::logits), the padding
+// actions a = 16 t + 4 g4 + q >= A masked to -inf whatever their bias reads
 template <int NT>
 __device__ __forceinline__ void greedy_logits(const Head<NT>& h, f4 a1, int A, int g4, float (&z)[NT][4]) {
-    float h1[4];
-#pragma unroll
-    for (int q = 0; q < 4; q++) h1[q] = fast_tanh_b(a1[q], h.b1[q]);
-    f4 a2 = {0, 0, 0, 0};
-#pragma unroll
-    for (int s = 0; s < 4; s++) a2 = mfma4(h.w2[s], h1[s], a2);
-    float h2[4];
-#pragma unroll
-    for (int q = 0; q < 4; q++) h2[q] = fast_tanh_b(a2[q], h.b2[q]);
-#pragma unroll
-    for (int t = 0; t < NT; t++) {
-        f4 zz = {0, 0, 0, 0};
-#pragma unroll
-        for (int s = 0; s < 4; s++) zz = mfma4(h.w3[t][s], h2[s], zz);
-#pragma unroll
-        for (int q = 0; q < 4; q++) z[t][q] = 16 * t + 4 * g4 + q < A ? zz[q] + h.b3[t][q] : -INFINITY;
-    }
+    h.logits(a1, z, [&](int t, int q, float v) { return 16 * t + 4 * g4 + q < A ? v : -INFINITY; });
 }
 
 // The first maximum of row j's logits, on every lane of the row, and (want_lp) its log-prob
@@ -114,33 +97,6 @@ __device__ __forceinline__ void greedy_pick(const float (&z)[NT][4], int g4, boo
     }
 }
 
-// layer 1 of a tile: lane (j, g4) holds dwords 8 s + 2 g4, 8 s + 2 g4 + 1 of row j, its B fragment of k-step s
-template <int S1>
-__device__ __forceinline__ f4 greedy_layer1(const W1Split<S1>& w1, const uint32_t (&xd)[S1][2]) {
-    f4 acc = {0, 0, 0, 0};
-#pragma unroll
-    for (int s = 0; s < S1; s++) {
-        const u4v x = bytes_to_bf16(xd[s][0], xd[s][1]);
-        acc = mfma_bf16(w1.hi[s], x, acc);
-        acc = mfma_bf16(w1.mid[s], x, acc);
-        acc = mfma_bf16(w1.lo[s], x, acc);
-    }
-    return acc;
-}
-
-// loads from clamped addresses, as act_tiles: the dwords past the row meet zero weights
-template <int S1>
-__device__ __forceinline__ void greedy_load(const RawBuf& b, uint32_t row_byte, int stride4, int g4,
-                                            uint32_t (&dst)[S1][2]) {
-#pragma unroll
-    for (int s = 0; s < S1; s++)
-#pragma unroll
-        for (int h = 0; h < 2; h++) {
-            const int cc = 8 * s + 2 * g4 + h;
-            dst[s][h] = b.ld32(row_byte + 4u * (uint32_t)(cc < stride4 ? cc : stride4 - 1));
-        }
-}
-
 // One wave = a contiguous range of 16-row tiles of one group (the next tile's rows prefetched in registers).
 // With a price net (NT2 > 0) the wave is FreePriceOfferPPO.selectAction with both picks greedy.
 template <int S1, int NT, int NT2>
@@ -186,7 +142,7 @@ __device__ __forceinline__ void greedy_tiles(const GreedyArgs& a, int block) {
     int row = -1;
     if (t0 < t1) {
         row = row_of(t0);
-        greedy_load<S1>(obs_b, (uint32_t)(row < 0 ? 0 : row) * (uint32_t)a.stride, stride4, g4, pre);
+        load_row<S1>(obs_b, (uint32_t)(row < 0 ? 0 : row) * (uint32_t)a.stride, stride4, g4, pre);
     }
     for (int tile = t0; tile < t1; tile++) {
         uint32_t xd[S1][2];
@@ -195,10 +151,10 @@ __device__ __forceinline__ void greedy_tiles(const GreedyArgs& a, int block) {
         const int cur = row;
         if (tile + 1 < t1) {
             row = row_of(tile + 1);
-            greedy_load<S1>(obs_b, (uint32_t)(row < 0 ? 0 : row) * (uint32_t)a.stride, stride4, g4, pre);
+            load_row<S1>(obs_b, (uint32_t)(row < 0 ? 0 : row) * (uint32_t)a.stride, stride4, g4, pre);
         }
         float z[NT][4];
-        greedy_logits<NT>(h1, greedy_layer1<S1>(w1, xd), A1, g4, z);
+        greedy_logits<NT>(h1, w1.layer1(xd), A1, g4, z);
         int act;
         float lp;
         greedy_pick<NT>(z, g4, want_lp, act, lp);
@@ -212,13 +168,13 @@ __device__ __forceinline__ void greedy_tiles(const GreedyArgs& a, int block) {
             const int k = g4 < 2 ? 2 * act + g4 : 2 * a.n_cores + (g4 - 2);
             const int byte = obs_b.ld8s((uint32_t)(cur < 0 ? 0 : cur) * (uint32_t)a.stride + (uint32_t)k);
             const int pin = act == 0 ? -5 : byte;
-            // the row's 4 bytes as the one dword a 4-byte row is (the clamped loads of greedy_load repeat it)
+            // the row's 4 bytes as the one dword a 4-byte row is (the clamped loads of load_row repeat it)
             uint32_t pb[4];
             rows_bcast((uint32_t)pin & 0xffu, pb);
             const uint32_t pd = pb[0] | (pb[1] << 8) | (pb[2] << 16) | (pb[3] << 24);
-            const uint32_t px[1][2] = {{pd, pd}};
             float z2[NP][4];
-            greedy_logits<NP>(h2, greedy_layer1<1>(w1p, px), a.n2.n_actions, g4, z2);
+            const uint32_t px[1][2] = {{pd, pd}};
+            greedy_logits<NP>(h2, w1p.layer1(px), a.n2.n_actions, g4, z2);
             int pact;
             float plp;
             greedy_pick<NP>(z2, g4, false, pact, plp);
@@ -261,9 +217,9 @@ __device__ __forceinline__ void greedy_common_rows(const GreedyArgs& a, int bloc
     float c_lp;
     {
         uint32_t xd[S1][2];
-        greedy_load<S1>(com_b, 0u, stride4, g4, xd);
+        load_row<S1>(com_b, 0u, stride4, g4, xd);
         float z[NT][4];
-        greedy_logits<NT>(h1, greedy_layer1<S1>(w1, xd), A, g4, z);
+        greedy_logits<NT>(h1, w1.layer1(xd), A, g4, z);
         greedy_pick<NT>(z, g4, want_lp, c_act, c_lp);
     }
     int32_t* list = s_list[wid];
@@ -311,9 +267,9 @@ __device__ __forceinline__ void greedy_common_rows(const GreedyArgs& a, int bloc
         int agent = 0;
         const int src = src_of(row, agent);
         uint32_t xd[S1][2];
-        greedy_load<S1>(obs_b, (uint32_t)src * (uint32_t)a.stride, stride4, g4, xd);
+        load_row<S1>(obs_b, (uint32_t)src * (uint32_t)a.stride, stride4, g4, xd);
         float z[NT][4];
-        greedy_logits<NT>(h1, greedy_layer1<S1>(w1, xd), A, g4, z);
+        greedy_logits<NT>(h1, w1.layer1(xd), A, g4, z);
         int act;
         float lp;
         greedy_pick<NT>(z, g4, want_lp, act, lp);
@@ -343,24 +299,13 @@ __global__ void __launch_bounds__(256) k_greedy_pair(GreedyArgs off, GreedyArgs 
         greedy_common_rows<S1b, NTb, true>(acc, (int)blockIdx.x - off_blocks);
 }
 
-// ---- launch shapes: ~target waves over all groups
+// ---- launch shapes (tile_blocks, common_blocks: ms_act_kernels.h); the scan has no draws to pair up, so
+//      a wave takes whole single 64-item steps
 static unsigned greedy_tile_blocks(GreedyArgs& a, long long target) {
-    const int G = a.n1.n_groups;
-    const int tiles = (a.n_items + 15) / 16;
-    const int tpw = (int)(((long long)tiles * G + target - 1) / target);
-    a.tiles_per_wave = tpw < 1 ? 1 : tpw;
-    a.waves_per_group = (tiles + a.tiles_per_wave - 1) / a.tiles_per_wave;
-    return (unsigned)(((long long)a.waves_per_group * G + 3) / 4);
+    return tile_blocks(a.n_items, a.n1.n_groups, target, &a.tiles_per_wave, &a.waves_per_group);
 }
-
 static unsigned greedy_common_blocks(GreedyArgs& a, long long target) {
-    const int G = a.n1.n_groups;
-    long long ipw = ((long long)a.n_items * G + target - 1) / target;
-    ipw = (ipw + 63) / 64 * 64;  // whole 64-item scan steps
-    ipw = ipw < 64 ? 64 : (ipw > kGreedySeg ? kGreedySeg : ipw);
-    a.items_per_wave = (int)ipw;
-    a.waves_per_group = (a.n_items + a.items_per_wave - 1) / a.items_per_wave;
-    return (unsigned)(((long long)a.waves_per_group * G + 3) / 4);
+    return common_blocks(a.n_items, a.n1.n_groups, target, 64, kGreedySeg, &a.items_per_wave, &a.waves_per_group);
 }
 
 constexpr long long kGreedyWaves = 4096, kGreedyCommonWaves = 2048;
@@ -373,14 +318,12 @@ static bool greedy_fits(const GreedyArgs& a) {
            a.n1.n_actions <= 128 && a.S >= 1 && a.n1.n_groups >= 1 && (long long)a.S * a.n1.n_groups == a.U;
 }
 
-static int pow2_steps(int n) { return n <= 1 ? 1 : (n <= 2 ? 2 : (n <= 4 ? 4 : (n <= 8 ? 8 : 0))); }
-
 template <int S1, int NT>
 static hipError_t launch_greedy_t(GreedyArgs& a, hipStream_t st) {
     if (a.n2.n_groups > 0) {
         // the core chooser has C + 1 <= 64 actions wherever the price chooser's input fits the row
         if constexpr (NT <= 4) {
-            const int nt2 = pow2_steps((a.n2.n_actions + 15) / 16);
+            const int nt2 = nt_bucket(a.n2.n_actions);
             const unsigned blocks = greedy_tile_blocks(a, kGreedyWaves);
             if (nt2 == 1)
                 hipLaunchKernelGGL((k_greedy<S1, NT, 1>), dim3(blocks), dim3(256), 0, st, a);
@@ -410,7 +353,7 @@ static hipError_t launch_greedy_t(GreedyArgs& a, hipStream_t st) {
 
 template <int S1>
 static hipError_t dispatch_greedy_s(GreedyArgs& a, hipStream_t st) {
-    switch (pow2_steps((a.n1.n_actions + 15) / 16)) {
+    switch (nt_bucket(a.n1.n_actions)) {
         case 1: return launch_greedy_t<S1, 1>(a, st);
         case 2: return launch_greedy_t<S1, 2>(a, st);
         case 4: return launch_greedy_t<S1, 4>(a, st);
@@ -426,7 +369,7 @@ static hipError_t dispatch_greedy(GreedyArgs& a, hipStream_t st) {
          a.n2.n_groups != a.n1.n_groups || 2 * a.n_cores + 2 > a.stride || a.n1.n_actions > a.n_cores + 1))
         return hipErrorInvalidValue;
     if (a.owner && (!a.common || a.n_cores < 1 || a.U % a.n_cores != 0)) return hipErrorInvalidValue;
-    switch (pow2_steps((a.stride + 31) / 32)) {
+    switch (s1_bucket(a.stride)) {
         case 1: return dispatch_greedy_s<1>(a, st);
         case 2: return dispatch_greedy_s<2>(a, st);
         case 4: return dispatch_greedy_s<4>(a, st);
@@ -481,9 +424,9 @@ hipError_t launch_act_round_greedy(const ms_mlp_params* core, const ms_mlp_param
     c.owner = core_owner;
     c.n_cores = n_cores;
     if (!common || !core_owner) return hipErrorInvalidValue;
-    const int s1a = pow2_steps((off_stride + 31) / 32), nta = pow2_steps((core->n_actions + 15) / 16);
-    const int nt2 = price ? pow2_steps((price->n_actions + 15) / 16) : 0;
-    const int s1b = pow2_steps((acc_stride + 31) / 32), ntb = pow2_steps((acc->n_actions + 15) / 16);
+    const int s1a = s1_bucket(off_stride), nta = nt_bucket(core->n_actions);
+    const int nt2 = price ? nt_bucket(price->n_actions) : 0;
+    const int s1b = s1_bucket(acc_stride), ntb = nt_bucket(acc->n_actions);
     const int shape = s1a == 1 && nta == 1 && nt2 == 0 && s1b == 1 && ntb == 1   ? 2
                       : s1a == 1 && nta == 1 && nt2 == 1 && s1b == 2 && ntb <= 2 ? 3
                       : s1a == 2 && nta <= 2 && nt2 == 1 && s1b == 4 && ntb <= 4 ? 4

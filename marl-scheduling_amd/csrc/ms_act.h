@@ -1,7 +1,9 @@
-// ms_act.h — the acting primitives shared by the act kernels (policy_kernels.hip) and the env round's
-// fused acting of fixed-price global nets (env_kernels.hip): Philox2x32 uniforms, the exact three-term
-// bf16 layer 1 (W1Split), the 16-wide head with its softmax / Categorical sampling (Head) and the act
-// fragment block layout (ms_act_prepare). PPOmodules.py:53-63 (ActorCritic.act).
+// ms_act.h — the forward pass of the acting nets, shared by the sampling and greedy act kernels
+// (ms_act_kernels.h, policy_kernels.hip, act_pair_kernels.hip, greedy_kernels.hip) and the env round's
+// fused acting of fixed-price global nets (env_kernels.hip): Philox2x32 uniforms, the clamped row load,
+// the exact three-term bf16 layer 1 (W1Split), the 16-wide head with its logits and its softmax /
+// Categorical sampling (Head) and the act fragment block layout (ms_act_prepare).
+// PPOmodules.py:53-63 (ActorCritic.act).
 //
 // Every includer gets the same floating-point contraction here (the policy kernels' -ffp-contract=fast),
 // whatever its own flags, so the fused acting of the env kernel (built with contraction off) rounds
@@ -48,8 +50,6 @@ __device__ __forceinline__ void philox2(uint32_t row, uint64_t off, uint64_t see
 
 __device__ __forceinline__ float u24(uint32_t r) { return (float)(r >> 8) * (1.0f / 16777216.0f); }
 
-__device__ __forceinline__ float xsum4g(float v) { return rows_sum(v); }
-
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef uint32_t u4v __attribute__((ext_vector_type(4)));
 
@@ -79,6 +79,35 @@ __device__ __forceinline__ uint32_t pack_hi(float lo, float hi) {
 }
 __device__ __forceinline__ float trunc_bf16(float x) { return __uint_as_float(__float_as_uint(x) & 0xffff0000u); }
 
+// int8 observation bytes (two dwords = 8 consecutive inputs) as a bf16 B fragment (exact)
+__device__ __forceinline__ u4v bytes_to_bf16(uint32_t d0, uint32_t d1) {
+    u4v r;
+#pragma unroll
+    for (int d = 0; d < 4; d++) {
+        const uint32_t src = d < 2 ? d0 : d1;
+        const int sh = 16 * (d & 1);
+        const float a = (float)(int8_t)(src >> sh);
+        const float b = (float)(int8_t)(src >> (sh + 8));
+        r[d] = pack_hi(a, b);
+    }
+    return r;
+}
+
+// A tile's rows as loaded: lane (j, g4) takes dwords 8s + 2 g4, 8s + 2 g4 + 1 of its row j, exactly its B
+// fragment of k-step s. Unconditional loads from clamped addresses, used as loaded: the dwords past the
+// row (stride4 dwords) repeat its last one and meet zero weights, so the wait lands at the use.
+template <int S1>
+__device__ __forceinline__ void load_row(const RawBuf& b, uint32_t row_byte, int stride4, int g4,
+                                         uint32_t (&dst)[S1][2]) {
+#pragma unroll
+    for (int s = 0; s < S1; s++)
+#pragma unroll
+        for (int h = 0; h < 2; h++) {
+            const int cc = 8 * s + 2 * g4 + h;
+            dst[s][h] = b.ld32(row_byte + 4 * (cc < stride4 ? cc : stride4 - 1));
+        }
+}
+
 // Layer-1 weights as three bf16 terms, w = hi + mid + lo exactly (truncation leaves exact residuals),
 // in the A-operand layout of v_mfma_f32_16x16x32_bf16 for k-step s: lane (i, g) holds
 // W1[i][32s + 8g + 0..7].
@@ -102,6 +131,21 @@ struct W1Split {
             lo[s] = *reinterpret_cast<const u4v*>(f + 12 * s + 8);
         }
     }
+    // Layer 1 of one tile (pre-activations without the bias) from its rows as load_row leaves them: per
+    // k-step the three terms' MFMAs, hi, mid, lo. The sampling kernels spell the same sequence out where
+    // they interleave two tiles or read the row from LDS (act_tiles, act_common_rows, common_table, the env
+    // round's fused acting): through this helper their register allocation changes.
+    __device__ __forceinline__ f4 layer1(const uint32_t (&xd)[S1][2]) const {
+        f4 acc = {0, 0, 0, 0};
+#pragma unroll
+        for (int s = 0; s < S1; s++) {
+            const u4v x = bytes_to_bf16(xd[s][0], xd[s][1]);
+            acc = mfma_bf16(hi[s], x, acc);
+            acc = mfma_bf16(mid[s], x, acc);
+            acc = mfma_bf16(lo[s], x, acc);
+        }
+        return acc;
+    }
     __device__ void load(const float* w1 /* [16][D] of this group */, int D, int i, int g) {
 #pragma unroll
         for (int s = 0; s < S1; s++) {
@@ -124,20 +168,6 @@ struct W1Split {
         }
     }
 };
-
-// int8 observation bytes (two dwords = 8 consecutive inputs) as a bf16 B fragment (exact)
-__device__ __forceinline__ u4v bytes_to_bf16(uint32_t d0, uint32_t d1) {
-    u4v r;
-#pragma unroll
-    for (int d = 0; d < 4; d++) {
-        const uint32_t src = d < 2 ? d0 : d1;
-        const int sh = 16 * (d & 1);
-        const float a = (float)(int8_t)(src >> sh);
-        const float b = (float)(int8_t)(src >> (sh + 8));
-        r[d] = pack_hi(a, b);
-    }
-    return r;
-}
 
 // The 16-wide layers and the head of one net, in registers: lane (j, g4) holds W2[j][4*g4 + s],
 // W3[16t + j][4*g4 + s] (the permuted-k A operands) and the biases of its accumulator rows.
@@ -189,12 +219,15 @@ struct Head {
         }
     }
 
-    // Layers 2-3 and the softmax numerators of the 16 rows of a tile given layer-1 pre-activations:
-    // z[t][q] = exp(logit - max) of action a = 16t + 4*g4 + q of row j, S = the row's sum of z and
-    // c[t][q] = the running sum of z over actions 0..a (in increasing action order). Logits of the
-    // padding actions (a >= A) read -inf (bias), so they drop out of the max and the sums.
-    __device__ __forceinline__ void numerators(f4 a1, int j, int g4, float (&z)[NT][4], float (&c)[NT][4],
-                                               float& S) const {
+    // Layers 2-3 of the 16 rows of a tile given layer-1 pre-activations: z[t][q] = the logit of action
+    // a = 16t + 4*g4 + q of row j. Logits of the padding actions (a >= A) read -inf (bias). Returns the
+    // largest of this lane's logits (what a softmax needs next; folded in as each logit is formed).
+    __device__ __forceinline__ float logits(f4 a1, float (&z)[NT][4]) const {
+        return logits(a1, z, [](int, int, float v) { return v; });
+    }
+    // (fix(t, q, logit) replaces each logit as it is formed: the greedy kernels' mask by action index)
+    template <class F>
+    __device__ __forceinline__ float logits(f4 a1, float (&z)[NT][4], F fix) const {
         float h1[4];
 #pragma unroll
         for (int q = 0; q < 4; q++) h1[q] = fast_tanh_b(a1[q], b1[q]);
@@ -212,10 +245,18 @@ struct Head {
             for (int s = 0; s < 4; s++) zz = mfma4(w3[t][s], h2[s], zz);
 #pragma unroll
             for (int q = 0; q < 4; q++) {
-                z[t][q] = zz[q] + b3[t][q];
+                z[t][q] = fix(t, q, zz[q] + b3[t][q]);
                 m = fmaxf(m, z[t][q]);
             }
         }
+        return m;
+    }
+
+    // The softmax numerators of the tile's rows: z[t][q] = exp(logit - max) of action a = 16t + 4*g4 + q
+    // of row j, S = the row's sum of z and c[t][q] = the running sum of z over actions 0..a (in increasing
+    // action order). The padding actions' -inf logits drop out of the max and the sums.
+    __device__ __forceinline__ void numerators(f4 a1, int g4, float (&z)[NT][4], float (&c)[NT][4], float& S) const {
+        float m = logits(a1, z);
         m = rows_max(m);
         float bs[NT];
         const float m_l2e = m * 1.4426950408889634f;
@@ -232,8 +273,8 @@ struct Head {
 #pragma unroll
         for (int t = 0; t < NT; t++) lane_tot += bs[t];
         // (one 16-action tile: S is the running sums' total, (gs0 + gs1) + (gs2 + gs3), which is
-        //  xsum4g(lane_tot) bit for bit)
-        if (NT > 1) S = xsum4g(lane_tot);
+        //  rows_sum(lane_tot) bit for bit)
+        if (NT > 1) S = rows_sum(lane_tot);
         float cum = 0.f;
 #pragma unroll
         for (int t = 0; t < NT; t++) {
@@ -309,7 +350,7 @@ struct Head {
         }
         int cnt[2];
         if (NT > 1) {
-            rows_sum2(S[0], S[1]);  // = xsum4g(lane_tot) of numerators()
+            rows_sum2(S[0], S[1]);  // = rows_sum(lane_tot) of numerators()
 #pragma unroll
             for (int i = 0; i < 2; i++) {
                 const float target = u[i] * S[i];
@@ -397,10 +438,10 @@ struct Head {
     // The sampling entries of the tile's 16 rows, one row per column j: lane (j, g4) gets its four
     // actions' running sums c and log-probs lp (what run() would compare and return), and S and the
     // last nonzero action of row j (every lane of the row).
-    __device__ __forceinline__ void row_table(f4 a1, int j, int g4, float (&c)[NT][4], float (&lp)[NT][4], float& S,
+    __device__ __forceinline__ void row_table(f4 a1, int g4, float (&c)[NT][4], float (&lp)[NT][4], float& S,
                                               int& last_nz) const {
         float z[NT][4];
-        numerators(a1, j, g4, z, c, S);
+        numerators(a1, g4, z, c, S);
         last_nz = last_nonzero(z, g4);
         const float rS = __builtin_amdgcn_rcpf(S);
 #pragma unroll
@@ -415,7 +456,7 @@ struct Head {
     __device__ __forceinline__ void table(f4 a1, int j, int g4, float* cum, float* lp, float* S_out,
                                           int* last_nz_out) const {
         float z[NT][4], c[NT][4], S;
-        numerators(a1, j, g4, z, c, S);
+        numerators(a1, g4, z, c, S);
         const int last_nz = last_nonzero(z, g4);
         if (j == 0) {
 #pragma unroll
