@@ -2607,7 +2607,7 @@ __global__ void __launch_bounds__(512, 4) k_env_rollout_act_free(RolloutFreeArgs
                                     ? reinterpret_cast<const int8_t*>(smem_free + fl.accx) + wave * kFreeEPW * g.N * g.C
                                     : nullptr;
         env_round<kWave / kFreeEPW, false, true, SH>(A.P, A.E, A.recs, A.mt, A.liab, io, wslot, lane,
-                                                     smem_free + wave * kFreeEPW * g.s_total, acc_lds);
+                                                     smem_free + wave * free_slot(g), acc_lds);
         if (up) __builtin_amdgcn_s_setprio(0);
         FREE_MARK(0);
         if (t + 1 < n_rounds || A.act_last) {
@@ -2899,11 +2899,10 @@ hipError_t launch_env_rollout_act(const Params& P, int64_t E, uint8_t* recs, uin
 }
 // ms_env_rollout_act_free: 16 lanes per replica (max(N, C) <= 16), one wave per agent (N <= 8: a 512-lane
 // workgroup), the core chooser one k-step with <= 16 actions, the acceptor two k-steps with 17..32 actions
-// (k_act_pair<1, 1, 1, 2, 2>'s shapes), the price chooser <= 16 actions, two workgroups' LDS per CU
+// (k_act_pair<1, 1, 1, 2, 2>'s shapes), the price chooser <= 16 actions, two workgroups' LDS per CU with every
+// wave's MT twist inside bytes no other wave uses (ms_layout.h)
 bool env_rollout_free_supported(const Params& P) {
-    return P.free_prices && P.N >= 1 && P.N <= 8 && P.C >= 1 && P.C <= 16 && P.off_stride <= 32 &&
-           P.C + 1 <= 16 && P.acc_stride > 32 && P.acc_stride <= 64 && P.O + 1 > 16 && P.O + 1 <= 32 &&
-           2 * (free_lds(P).total + 256) <= 160 * 1024;
+    return P.free_prices && free_rollout_shape_ok(P) && free_rollout_lds_ok(P);
 }
 template <class SH>
 static hipError_t launch_rollout_free_sh(const Params& P, int64_t E, uint8_t* recs, uint32_t* mt, Liab* liab,

@@ -223,9 +223,14 @@ constexpr int kFreeTabDw = 68;     // [32 running sums][32 log-probs][S][last no
 struct FreeLds {
     int32_t pdig, list, accx, pace, total;
 };
+// A wave's env slot. At the start of a round the wave may twist an MT block in it (mt_refill_groups writes
+// 4 * kMtN bytes from the slot's start, before the round stages anything there), while the other waves' slots
+// and the act area are live: the twist has to end inside the slot, or, for the last wave, below pdig.
+inline constexpr int32_t free_slot(const Geom& g) { return kFreeEPW * g.s_total; }
 inline constexpr FreeLds free_lds(const Geom& g) {
     FreeLds f{};
-    f.pdig = align16(kFreeEPW * g.N * g.s_total);
+    const int32_t slots = g.N * free_slot(g), twist_end = (g.N - 1) * free_slot(g) + 4 * kMtN;
+    f.pdig = align16(slots > twist_end ? slots : twist_end);
     f.list = f.pdig + 4 * 256 * 2;
     f.accx = align16(f.list + g.N * kFreeListCap * 6);  // int16 item + f32 uniform per entry
     // (by-core mode) the replicas' acceptor actions [kFreeEPW * N][N * C]: the acting writes its owned items, the
@@ -233,6 +238,19 @@ inline constexpr FreeLds free_lds(const Geom& g) {
     f.pace = f.accx + align4(kFreeEPW * g.N * g.N * g.C);
     f.total = f.pace + 4 * 8;  // (MS_FREE_PRIO bit 2) each wave's count of acting steps done
     return f;
+}
+// The shapes k_env_rollout_act_free is built for (env_rollout_free_supported): 16 lanes per replica
+// (max(N, C) <= 16), one wave per agent (N <= 8: a 512-lane workgroup), the core chooser one k-step with <= 16
+// actions, the acceptor two k-steps with 17..32 actions (k_act_pair<1, 1, 1, 2, 2>'s shapes)
+inline constexpr bool free_rollout_shape_ok(const Geom& g) {
+    return g.N >= 1 && g.N <= 8 && g.C >= 1 && g.C <= 16 && g.off_stride <= 32 && g.C + 1 <= 16 &&
+           g.acc_stride > 32 && g.acc_stride <= 64 && g.O + 1 > 16 && g.O + 1 <= 32;
+}
+// ... and its LDS: two workgroups per CU (160 KiB; 256 B for the kernel's static arrays), and every wave but
+// the last twists inside its own slot (the last wave's twist ends below pdig by free_lds)
+constexpr int32_t kFreeLdsBudget = 160 * 1024;
+inline constexpr bool free_rollout_lds_ok(const Geom& g) {
+    return 2 * (free_lds(g).total + 256) <= kFreeLdsBudget && (g.N == 1 || free_slot(g) >= 4 * kMtN);
 }
 
 // launch arguments of k_aggregate_obs (agg_kernels.hip): divided rows in, aggregated rows out

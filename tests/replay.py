@@ -13,9 +13,19 @@ def _ppo():
     return importlib.import_module("marl-scheduling_amd.ppo")
 
 
-def oracle_replay(tr, replicas, base_seed, T):
+def set_mt_index(env, mt_index):
+    """Move an env's MT19937 stream to index mt_index of its current block (a BatchedEnv: every replica's;
+    or one OracleEnv), by export_state / import_state."""
+    st = env.export_state()
+    st["mt_index"] = np.full_like(st["mt_index"], mt_index)
+    env.import_state(st)
+
+
+def oracle_replay(tr, replicas, base_seed, T, mt_index=None):
     """Step the C oracle of replicas e with the actions the trainer's rings hold and compare its
-    observations and rewards with the rings (slot t + 1 = the observation after round t)."""
+    observations and rewards with the rings (slot t + 1 = the observation after round t).
+    mt_index: the oracle envs start at that index of their first MT19937 block, like a trainer whose
+    replicas were moved there before the rollout (set_mt_index)."""
     cfg = tr.cfg
     s = pyoracle.abi.config_shape(cfg)
     N, C, L, D_acc, D_off = s["N"], s["C"], s["L"], s["acc_obs_dim"], s["off_obs_dim"]
@@ -32,6 +42,8 @@ def oracle_replay(tr, replicas, base_seed, T):
     rp = tr.price.rewards[:, list(replicas)].cpu().numpy() if tr.free else None
     for i, e in enumerate(replicas):
         env = pyoracle.OracleEnv(cfg, base_seed + e)
+        if mt_index is not None:
+            set_mt_index(env, mt_index)
         o = env.observe()
         assert np.array_equal(acc_all[0, i, :, :D_acc].reshape(N, C, D_acc), o["acceptor"]), e
         for t in range(T):

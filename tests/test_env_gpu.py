@@ -7,7 +7,8 @@ import numpy as np
 import pytest
 import torch
 
-from tests.drivers import offer_counts_from_obs, random_actions
+from tests.drivers import compare_state as _compare_state
+from tests.drivers import offer_counts_from_obs, random_actions, step_rounds_vs_oracle
 
 pytestmark = pytest.mark.gpu
 
@@ -29,65 +30,13 @@ def _cfg(abi, name):
     return abi.named_config(name) if kw is None else abi.make_config(**kw)
 
 
-def _compare_state(gs, os_list, E):
-    for e in range(E):
-        o = os_list[e]
-        for k in ("round", "core_owner", "core_kind", "core_rem", "core_birth", "slot_kind", "slot_rem",
-                  "slot_wait", "slot_birth", "offer_core", "offer_recip", "offer_price", "liab_n", "mt_index"):
-            np.testing.assert_array_equal(gs[k][e], o[k], err_msg="%s env %d" % (k, e))
-        np.testing.assert_array_equal(gs["mt"][e], o["mt"], err_msg="mt env %d" % e)
-        for c in range(gs["liab_n"].shape[1]):
-            n = gs["liab_n"][e, c]
-            np.testing.assert_array_equal(gs["liab"][e, c, :n], o["liab"][c, :n])
-
-
 @pytest.mark.parametrize("name", list(CONFIGS))
 def test_step_bit_exact_vs_oracle(ms, oracle, name):
-    abi = ms.abi
-    cfg = _cfg(abi, name)
-    s = abi.config_shape(cfg)
-    N, C, L, O = s["N"], s["C"], s["L"], s["O"]
+    cfg = _cfg(ms.abi, name)
     E, T, seed = 24, 240, 7
     genv = ms.BatchedEnv(cfg, E, seed=seed)
     oenvs = [oracle.OracleEnv(cfg, seed + e) for e in range(E)]
-    dev = genv.device
-    obs = genv.reset(genv.obs_buffers(auctioneer=True))
-    oobs = [o.observe() for o in oenvs]
-    rng = np.random.default_rng(3)
-    free = bool(cfg.free_prices)
-    for t in range(T):
-        acts = [random_actions(rng, offer_counts_from_obs(oobs[e]["acceptor"], O), N, C, L, O, free,
-                               s["price_actions"] - 1, accept_bias=0.7) for e in range(E)]
-        acc = torch.tensor(np.stack([a[0] for a in acts]), dtype=torch.int8, device=dev)
-        off = torch.tensor(np.stack([a[1] for a in acts]), dtype=torch.int8, device=dev)
-        pr = torch.tensor(np.stack([a[2] for a in acts]), dtype=torch.int8, device=dev) if free else None
-        ev = genv.event_buffers()
-        gobs, grew, gev = genv.step(acc, off, pr, obs=genv.obs_buffers(auctioneer=True), events=ev)
-        ores = [oenvs[e].step(*acts[e]) for e in range(E)]
-        oobs = [o.observe() for o in oenvs]
-        ga = gobs["acceptor"].cpu().numpy()
-        gof = gobs["offer"].cpu().numpy()
-        gau = gobs["auctioneer"].cpu().numpy()
-        for e in range(E):
-            np.testing.assert_array_equal(ga[e, :, :, : s["acc_obs_dim"]], oobs[e]["acceptor"], err_msg="acc obs t=%d e=%d" % (t, e))
-            assert (ga[e, :, :, s["acc_obs_dim"]:] == 0).all()
-            np.testing.assert_array_equal(gof[e, :, :, : s["off_obs_dim"]], oobs[e]["offer"], err_msg="off obs t=%d e=%d" % (t, e))
-            np.testing.assert_array_equal(gau[e, :, : s["acc_obs_dim"]], oobs[e]["auctioneer"], err_msg="auct obs t=%d" % t)
-            np.testing.assert_array_equal(grew["acceptor"][e].cpu().numpy(), ores[e]["acceptor"], err_msg="acc rew t=%d e=%d" % (t, e))
-            np.testing.assert_array_equal(grew["offer"][e].cpu().numpy(), ores[e]["offer"])
-            if free:
-                np.testing.assert_array_equal(grew["price"][e].cpu().numpy(), ores[e]["price"])
-            np.testing.assert_array_equal(grew["auctioneer"][e].cpu().numpy(), ores[e]["auctioneer"])
-            np.testing.assert_array_equal(grew["agent"][e].cpu().numpy(), ores[e]["agent"])
-            gacc = ms.decode_accepted(gev["accepted"][e])
-            gterm = ms.decode_terminated(gev["terminated"][e])
-            for f in ("valid", "offerer", "recipient", "slot", "price", "nec_time", "prio", "kind", "order", "round"):
-                np.testing.assert_array_equal(gacc[f][gacc["valid"] == 1], ores[e]["accepted"][f][ores[e]["accepted"]["valid"] == 1])
-            np.testing.assert_array_equal(gacc["valid"], ores[e]["accepted"]["valid"])
-            for f in ("valid", "owner", "prio", "init_len", "dwell"):
-                np.testing.assert_array_equal(gterm[f], ores[e]["terminated"][f])
-        if t % 40 == 0 or t == T - 1:
-            _compare_state(genv.export_state(), [o.export_state() for o in oenvs], E)
+    step_rounds_vs_oracle(ms, genv, oenvs, T, np.random.default_rng(3), state_every=40)
     assert genv.flags() == 0
     assert genv.round == T
 

@@ -36,7 +36,8 @@ def _trainers(monkeypatch, mk):
     return fused, plain
 
 
-def _compare(trs, iters=2):
+def _compare(trs, iters=2, after_rollout=None):
+    """after_rollout(it): further checks on the compared rings of iteration it, before its update."""
     for it in range(iters):
         for t in trs:
             t.rollout()
@@ -45,6 +46,8 @@ def _compare(trs, iters=2):
         for k in r0:
             same = r0[k] == r1[k]
             assert bool(same.all()), (it, k, int((~same).sum()), same.numel())
+        if after_rollout is not None:
+            after_rollout(it)
         losses = [t.update() for t in trs]
         for k in losses[0]:
             assert torch.equal(losses[0][k], losses[1][k]), (it, k)
