@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define MS_ABI_VERSION 19
+#define MS_ABI_VERSION 20
 
 #define MS_MAX_KINDS 16
 #define MS_MAX_AGENTS 64
@@ -581,6 +581,27 @@ typedef struct ms_ppo_batch {
     /* 0: states [R][U][stride], actions / old_logprobs [R][U]; else >= R and unit-major: row (r, u) at
      * u * unit_stride + r in all three (e.g. [U][T][E] rollout rings; not with core_owner) */
     int64_t unit_stride;
+    /* (ABI 20) regenerate: with compact rows of a one-launch free-price rollout (ms_env_rollout_act_free with
+     * own_action / own_logprob), the gradient can do without the acceptor rings' items of ring slots
+     * >= regen_slot0. A row (r = t*E + e, unit a*C + c) of a core the agent owns takes its action and old
+     * log-prob from own_action / own_logprob [R][n_cores] at (r, c); every other row's pair is what
+     * ms_env_rollout_fill_common would have written, recomputed from its Philox draw (regen_seed, offset
+     * regen_offset + t * regen_offset_step + *regen_offset_dev, regen_row_base = the acceptor net's row_base) and
+     * agent a's common-row table in regen_frag (the acceptor's act fragment block as it was at acting time).
+     * actions / old_logprobs are then read for ring slots < regen_slot0 only (slot 0 is acted by
+     * ms_act_round_free, which writes whole rows). Gradients and loss terms are bit-identical to reading
+     * complete rings. regen_frag NULL (and the rest 0 / NULL): every row from actions / old_logprobs.
+     * MS_EINVAL without core_owner / common_row / both own arrays, or outside the fill's shapes (one net per
+     * agent, N <= 8, rows of 33..64 bytes with in_dim < 64, 17..32 actions). */
+    const void* regen_frag;
+    const int8_t* own_action;        /* [R][n_cores] */
+    const float* own_logprob;        /* [R][n_cores] */
+    uint64_t regen_seed;
+    uint64_t regen_offset;           /* the acting offset of ring slot 0 */
+    const uint64_t* regen_offset_dev;  /* optional device counter added to it (as offset_dev at acting time) */
+    uint64_t regen_offset_step;      /* offset advance per ring slot */
+    int64_t regen_row_base;
+    int32_t regen_slot0;             /* first regenerated ring slot, in [0, T] */
 } ms_ppo_batch;
 
 typedef struct ms_ppo_grads {  /* device outputs, [G][...] like the weights */

@@ -282,6 +282,16 @@ class MsPpoBatch(ct.Structure):
         ("n_cores", ct.c_int32),
         ("row_keys", ct.c_int32),
         ("unit_stride", ct.c_int64),
+        # ABI 20: the regenerating acceptor scan (all NULL / 0: every row from actions / old_logprobs)
+        ("regen_frag", ct.c_void_p),
+        ("own_action", ct.c_void_p),
+        ("own_logprob", ct.c_void_p),
+        ("regen_seed", ct.c_uint64),
+        ("regen_offset", ct.c_uint64),
+        ("regen_offset_dev", ct.c_void_p),
+        ("regen_offset_step", ct.c_uint64),
+        ("regen_row_base", ct.c_int64),
+        ("regen_slot0", ct.c_int32),
     ]
 
 

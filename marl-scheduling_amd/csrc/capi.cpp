@@ -33,6 +33,7 @@ hipError_t launch_env_rollout_act(const Params&, int64_t, uint8_t*, uint32_t*, L
 hipError_t launch_env_rollout_act_free(const Params&, int64_t, uint8_t*, uint32_t*, Liab*, const StepIO&,
                                        const FusedActFree&, const RoundStrideFree&, int, int, hipStream_t);
 bool env_rollout_free_supported(const Params&);
+void acc_common_tables(const void*, const uint32_t**, int*);
 hipError_t launch_env_fill_common(const Params&, int64_t, const StepIO&, const FusedActFree&, const RoundStrideFree&,
                                   int, int, hipStream_t);
 hipError_t launch_env_randbelow(const Params&, uint8_t*, uint32_t*, int64_t, uint32_t, uint32_t*, hipStream_t);
@@ -983,6 +984,36 @@ int ms_ppo_grad(const ms_mlp_params* a, const ms_mlp_params* c, const ms_ppo_bat
     p.P = ms::ppo_param_count(p.D, p.A);
     p.eps_clip = eps_clip;
     p.inv_R = 1.0f / (float)R;
+    const bool regen_any = b->regen_frag || b->own_action || b->own_logprob || b->regen_offset_dev || b->regen_seed ||
+                           b->regen_offset || b->regen_offset_step || b->regen_row_base || b->regen_slot0;
+    if (regen_any) {
+        static_assert(ms::kRegenTabDw == ms::kFreeTabDw, "the common-row table's size");
+        if (!b->core_owner || !b->common_row) return fail(MS_EINVAL, "regenerate needs compact rows (core_owner, common_row)");
+        if (!b->regen_frag || !b->own_action || !b->own_logprob)
+            return fail(MS_EINVAL, "regenerate needs regen_frag, own_action and own_logprob");
+        const int N = b->U / b->n_cores;
+        // what ms_env_rollout_fill_common samples: one net per agent, FragLayout<2, 2> tables
+        if (a->n_groups != N || N > 8 || b->n_cores > 16 || b->stride < 36 || b->stride > 64 || a->in_dim >= 64 ||
+            a->n_actions < 17 || a->n_actions > 32)
+            return fail(MS_EINVAL, "regenerate: one net per agent, N <= 8, C <= 16, rows of 33..64 bytes (in_dim < 64), "
+                                   "17..32 actions only");
+        if (b->regen_slot0 < 0 || b->regen_slot0 > b->T) return fail(MS_EINVAL, "regen_slot0 must be in [0, T]");
+        // 32-bit item and Philox row arithmetic (as the fill), and a wave's rows within magic_div(E)'s range
+        if (b->E * (int64_t)b->U * b->n_cores >= (1LL << 32) ||
+            (b->E + 64LL * p.chunk_tiles) * b->E >= (1LL << 32))
+            return fail(MS_EINVAL, "regenerate: too many replicas for 32-bit row arithmetic");
+        ms::acc_common_tables(b->regen_frag, &p.rg_tab, &p.rg_tab_gs);
+        p.rg_slot0 = b->regen_slot0;
+        p.rg_row_base = (uint32_t)b->regen_row_base;
+        p.rg_mag_E = ms::magic_div((uint32_t)b->E);
+        p.rg_mag_C = ms::magic_div((uint32_t)b->n_cores);
+        p.rg_own_act = b->own_action;
+        p.rg_own_lp = b->own_logprob;
+        p.rg_seed = b->regen_seed;
+        p.rg_offset = b->regen_offset;
+        p.rg_step = b->regen_offset_step;
+        p.rg_offset_dev = b->regen_offset_dev;
+    }
     if (ppo_keyable(a) && b->row_keys == 0) {
         const KeyWs k = key_ws(a, R);
         uint8_t* w = (uint8_t*)ws + ppo_partials_bytes(a, R);

@@ -2947,6 +2947,15 @@ static bool fill_quad_enabled() {
     }();
     return v;
 }
+// where the fill kernels read the agents' common-row tables in an acceptor act fragment block (FragLayout<2, 2>,
+// ms_act_prepare with a common row): agent 0's table and the dwords between two agents' tables. The PPO
+// gradient's regenerating scan (ms_ppo_batch regen_frag) stages the same words.
+void acc_common_tables(const void* act_frag, const uint32_t** tab0, int* group_dwords) {
+    using FL = FragLayout<2, 2>;
+    static_assert(FL::TB == kFreeTabDw, "common table size");
+    *tab0 = static_cast<const uint32_t*>(act_frag) + 4 + 64 * FL::LW;
+    *group_dwords = FL::GB;
+}
 // the acceptor items of cores their agent does not own, every acting round of a k_env_rollout_act_free launch
 // with the same arguments (its outputs' other items are untouched)
 hipError_t launch_env_fill_common(const Params& P, int64_t E, const StepIO& io, const FusedActFree& fa,

@@ -23,32 +23,7 @@ namespace ms {
 typedef float f4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ f4 mfma4(float a, float b, f4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
 
-__device__ __forceinline__ uint32_t mulhilo(uint32_t a, uint32_t b, uint32_t& hi) {
-    uint64_t p = (uint64_t)a * b;
-    hi = (uint32_t)(p >> 32);
-    return (uint32_t)p;
-}
-
-// Philox2x32-10 (Salmon et al., SC'11, the 2-word member of the family; BigCrush-clean from 7 rounds):
-// two 32-bit outputs per (counter, key). The counter is (row, offset low word); the key folds in
-// the 64-bit seed and the offset's high word. Half the multiplies of Philox4x32 for the two words
-// a row needs (the act kernels' VALU budget: a 32-bit multiply issues at a quarter of the rate).
-__device__ __forceinline__ void philox2(uint32_t row, uint64_t off, uint64_t seed, uint32_t& o0, uint32_t& o1) {
-    uint32_t c0 = row, c1 = (uint32_t)off;
-    uint32_t k = (uint32_t)seed ^ ((uint32_t)(seed >> 32) * 0x85EBCA6Bu) ^ ((uint32_t)(off >> 32) * 0xC2B2AE35u);
-#pragma unroll
-    for (int r = 0; r < 10; r++) {
-        uint32_t hi;
-        const uint32_t lo = mulhilo(0xD256D193u, c0, hi);
-        c0 = hi ^ k ^ c1;
-        c1 = lo;
-        k += 0x9E3779B9u;
-    }
-    o0 = c0;
-    o1 = c1;
-}
-
-__device__ __forceinline__ float u24(uint32_t r) { return (float)(r >> 8) * (1.0f / 16777216.0f); }
+// (mulhilo, philox2 and u24 live in ms_common.h: the PPO gradient regenerates acting draws with them)
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef uint32_t u4v __attribute__((ext_vector_type(4)));

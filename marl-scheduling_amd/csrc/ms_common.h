@@ -1,4 +1,5 @@
-// ms_common.h — the cooperative row scan shared by the common-row act and PPO-gradient kernels.
+// ms_common.h — the cooperative row scan shared by the common-row act and PPO-gradient kernels, the lane-row
+// reductions, raw buffers and the acting draws (Philox2x32, which the PPO gradient's regenerating scan repeats).
 //
 // A 64-row scan step asks, for every row, whether it equals the common row (the acceptor row of
 // a core the agent does not own, Agent.py:167-212). LPR lanes read one row with 16-byte loads:
@@ -97,6 +98,34 @@ __device__ __forceinline__ void rows_bcast(uint32_t v, uint32_t (&r)[4]) {
     swap32(a, r[0], r[2]);    // rows 0 and 2 everywhere
     swap32(b, r[1], r[3]);    // rows 1 and 3
 }
+
+// ---- the acting kernels' random numbers (shared with the PPO gradient, which regenerates acting draws)
+__device__ __forceinline__ uint32_t mulhilo(uint32_t a, uint32_t b, uint32_t& hi) {
+    uint64_t p = (uint64_t)a * b;
+    hi = (uint32_t)(p >> 32);
+    return (uint32_t)p;
+}
+
+// Philox2x32-10 (Salmon et al., SC'11, the 2-word member of the family; BigCrush-clean from 7 rounds):
+// two 32-bit outputs per (counter, key). The counter is (row, offset low word); the key folds in
+// the 64-bit seed and the offset's high word. Half the multiplies of Philox4x32 for the two words
+// a row needs (the act kernels' VALU budget: a 32-bit multiply issues at a quarter of the rate).
+__device__ __forceinline__ void philox2(uint32_t row, uint64_t off, uint64_t seed, uint32_t& o0, uint32_t& o1) {
+    uint32_t c0 = row, c1 = (uint32_t)off;
+    uint32_t k = (uint32_t)seed ^ ((uint32_t)(seed >> 32) * 0x85EBCA6Bu) ^ ((uint32_t)(off >> 32) * 0xC2B2AE35u);
+#pragma unroll
+    for (int r = 0; r < 10; r++) {
+        uint32_t hi;
+        const uint32_t lo = mulhilo(0xD256D193u, c0, hi);
+        c0 = hi ^ k ^ c1;
+        c1 = lo;
+        k += 0x9E3779B9u;
+    }
+    o0 = c0;
+    o1 = c1;
+}
+
+__device__ __forceinline__ float u24(uint32_t r) { return (float)(r >> 8) * (1.0f / 16777216.0f); }
 
 // ---- an array addressed as a raw buffer: a wave-uniform base in scalar registers and 32-bit per-lane
 // byte offsets (no 64-bit address arithmetic per access; a 32-bit multiply is a quarter-rate VALU

@@ -58,7 +58,21 @@ struct PpoArgs {
     float* own_cfwd;       // [G][16*NT + 4] the common row's clamped log-probs, V, entropy
     float* own_csum;       // [G][16*NT + 8] the group's common-row sums (k_own_common)
     float own_qbound;      // a larger |term| marks the row for the tiles (|sum| * 2^28 < 2^63)
+    // regenerating scan (kOwnerRow, ms_ppo_batch's regen_* fields): from ring slot rg_slot0 on, a common row's
+    // action and old log-prob are k_acc_common_fill's sample (the row's Philox draw searched in the agent's
+    // act-time table) and an own row's come from the rollout's by-core arrays; actions / old_lp are read for
+    // the earlier slots only
+    const uint32_t* rg_tab;    // agent 0's common-row table (kRegenTabDw dwords), NULL: the rings for every row
+    int rg_tab_gs;             // dwords between two agents' tables
+    int rg_slot0;
+    uint32_t rg_row_base;
+    uint32_t rg_mag_E, rg_mag_C;  // magic_div(E), magic_div(owner_C) (ms_layout.h)
+    const int8_t* rg_own_act;  // [R][owner_C]
+    const float* rg_own_lp;    // [R][owner_C]
+    uint64_t rg_seed, rg_offset, rg_step;  // ring slot s acted with offset rg_offset + s * rg_step (+ *rg_offset_dev)
+    const uint64_t* rg_offset_dev;
 };
+constexpr int kRegenTabDw = 68;  // Head<2>::table: [32 running sums][32 log-probs][S][last nonzero][2 pad]
 
 constexpr int kOwnMinGroups = 64;     // groups from which compact rows take k_own_scan + kMaskRow
 constexpr int kOwnScanRows = 1024;    // rows per scan wave (a multiple of 32: whole mask words)

@@ -130,6 +130,10 @@ struct BoolC {
 // of a group's distinct rows, k_key_scan sums the rows' loss derivatives in between)
 enum GradMode { kPlain = 0, kCommonRow = 1, kOwnerRow = 2, kKeyBack = 3, kKeyFwd = 4, kMaskRow = 5, kCommonFwd = 6 };
 constexpr int kX1 = 16;  // mode bit: the last action tile has exactly one action (k_ppo_grad)
+// mode bit (kOwnerRow, <4, 2> only): the scan regenerates the common rows' actions and old log-probs from their
+// Philox draws and the agent's act-time table and takes the own rows' from the rollout's by-core arrays
+// (PpoArgs rg_*), instead of reading every row's from the [R][U] rings
+constexpr int kRegen = 32;
 // kMaskRow: compact acceptor rows of many groups (the divided acceptors), the common rows already
 // summed by k_own_scan / k_own_common: each wave runs the tiles of the rows its group's own-row mask
 // lists, and one wave per group the common rows' virtual tile. kCommonFwd: the forward of the
@@ -149,6 +153,7 @@ __device__ unsigned long long g_grad_probe[kGradProbeWaves][4];
 template <int NQ, int NT, int MODEX>
 struct GradLds {
     static constexpr int MODE = MODEX & 15;  // (bit 4: kX1, see k_ppo_grad)
+    static constexpr bool RG = (MODEX & kRegen) != 0;  // the agent's common-row table behind the biases
     static constexpr bool CM = MODE == kCommonRow || MODE == kOwnerRow;
     static constexpr bool ML = MODE == kMaskRow;
     static constexpr int S1 = (NQ + 1) / 2;           // 32-input k-steps of layer 1 (16*NQ inputs)
@@ -159,7 +164,7 @@ struct GradLds {
     static constexpr int NTR = NT + 1;               // 16-row transposes live at once (three phases per tile)
     // block: split W1 / C1 [2][3][16][W1B] bf16, then W2, C2, W3 and the biases (floats)
     static constexpr int w1s_floats = 2 * 3 * 16 * W1B / 2;
-    static constexpr int shared_floats = w1s_floats + 2 * 256 + 256 * NT + 16 * 5 + 16 * NT + 4;
+    static constexpr int shared_floats = w1s_floats + 2 * 256 + 256 * NT + 16 * 5 + 16 * NT + 4 + (RG ? kRegenTabDw : 0);
     // per wave: d1 / e1 transposes over a tile pair, the per-tile transposes, 32 staged input rows
     // (common-row path: the common row's clamped logs, V, entropy, the list of the other rows,
     //  and the wave's int64 fixed-point sums of d min(surr)/d ratio * ratio per action [16*NT])
@@ -180,6 +185,8 @@ __global__ void __launch_bounds__((64 * GradLds<NQ, NT, MODEX>::WPB), ((NQ * NT 
     // cfg4): its layer-3 row, backward term and weight gradient run on the VALU (4 FMAs per lane and a
     // sum over the row's lane groups) instead of 12 f32 MFMAs on a tile of 15 padding actions
     constexpr bool X1 = (MODEX & kX1) != 0;
+    constexpr bool RG = L::RG;
+    static_assert(!RG || (MODE == kOwnerRow && L::S1 == 2 && NT == 2), "the regenerating scan: FragLayout<2, 2> tables");
     constexpr int TP = L::TP, TP2 = L::TP2, XPD = L::XPD, S1 = L::S1, W1B = L::W1B;
     constexpr int NTH = 64 * L::WPB, CPW = 4 / L::WPB;  // threads per block, chunks per wave
     // the wave index through readfirstlane: everything derived from it (chunk, tile range, row buffers)
@@ -216,6 +223,7 @@ __global__ void __launch_bounds__((64 * GradLds<NQ, NT, MODEX>::WPB), ((NQ * NT 
     float* scb2 = scb1 + 16;            // 16
     float* sb3 = scb2 + 16;             // 16*NT
     float* scb3 = sb3 + 16 * NT;        // 1 (+3 pad)
+    const float* sTab = scb3 + 4;       // (kRegen) the agent's common-row table [kRegenTabDw], 16-byte aligned
     float* sT = sm + L::shared_floats + wave * L::wave_floats;
     float* T_d1 = sT;                   // [16 features][TP2]: 32 rows of the tile pair
     float* T_e1 = sT + 16 * TP2;
@@ -263,6 +271,10 @@ __global__ void __launch_bounds__((64 * GradLds<NQ, NT, MODEX>::WPB), ((NQ * NT 
             scb2[tid] = p.cb2[grp * 16 + tid] * kTanhScale;
         }
         if (tid == 0) scb3[0] = p.cb3[grp];
+        if constexpr (RG) {
+            const uint32_t* tab = p.rg_tab + (size_t)(u / p.owner_C) * p.rg_tab_gs;
+            for (int i = tid; i < kRegenTabDw; i += NTH) scb3[4 + i] = __uint_as_float(tab[i]);
+        }
     }
     __syncthreads();
     f4 gW1[NQ], gC1[NQ], gW3[NT];
@@ -1046,6 +1058,48 @@ __global__ void __launch_bounds__((64 * GradLds<NQ, NT, MODEX>::WPB), ((NQ * NT 
             __builtin_amdgcn_make_buffer_rsrc(const_cast<int8_t*>(MODE == kOwnerRow ? p.owner + (size_t)rb * p.owner_C + own_c
                                                                                      : p.actions),
                                               0, MODE == kOwnerRow ? (int)((re - rb) * p.owner_C) : 0, 0x00020000);
+        // (kRegen) rows from rg_r0 on take no action / log-prob from the rings: row r = t * E + e is replica e's
+        // acting of ring slot t. An own row reads the rollout's by-core pair (r, own_c); a common row's pair is
+        // k_acc_common_fill's sample, bit for bit: item i = e * C + c takes word (i >> 6) & 1 of the draw
+        // countered by the row of item i & ~64, the count of the agent's running sums <= u * S is the action
+        // (the last nonzero one past the end) and the table's log-prob of it the old log-prob. The round is
+        // per lane: a 64-row step may straddle two rounds.
+        const int rg_r0 = RG ? (int)min((long long)p.rg_slot0 * p.E, (long long)R) : 0;
+        const uint32_t rg_E = (uint32_t)p.E;
+        const uint32_t rg_tb = RG ? (uint32_t)rb / rg_E : 0u, rg_eb = RG ? (uint32_t)rb - rg_tb * rg_E : 0u;
+        const uint64_t rg_off0 = RG ? p.rg_offset + (p.rg_offset_dev ? *p.rg_offset_dev : 0ull) : 0ull;
+        const int8_t* rga_ring = ac_base + (size_t)rb * (size_t)p.rrs;
+        const float* rgl_ring = lp_base + (size_t)rb * (size_t)p.rrs;
+        const int8_t* rga_own = RG ? p.rg_own_act + (size_t)rb * p.owner_C + own_c : nullptr;
+        const float* rgl_own = RG ? p.rg_own_lp + (size_t)rb * p.owner_C + own_c : nullptr;
+        // row rb + rel's stored pair: the rings before rg_r0, the by-core arrays from it on (rel of a valid row)
+        auto rg_load = [&](uint32_t rel, int& act, float& olp) {
+            const bool ring = (int)rel + rb < rg_r0;
+            const uint32_t o = __umul24(rel, ring ? (uint32_t)p.rrs : (uint32_t)p.owner_C);
+            act = (ring ? rga_ring : rga_own)[o];
+            olp = (ring ? rgl_ring : rgl_own)[o];
+        };
+        auto regen = [&](int r, int& act, float& olp) {
+            // rb's replica + the row's distance: below E + the wave's rows, in rg_mag_E's range (checked by the host)
+            const uint32_t er = rg_eb + (uint32_t)(r - rb);
+            const uint32_t dt = rg_E == 1u ? er : __umulhi(er, p.rg_mag_E), e = er - dt * rg_E;
+            const uint32_t C = (uint32_t)p.owner_C;
+            const uint32_t i = e * C + (uint32_t)own_c, ib = i & ~64u;
+            const uint32_t eb = C == 1u ? ib : __umulhi(ib, p.rg_mag_C);
+            uint32_t w0, w1;
+            philox2(eb * (uint32_t)p.U + (uint32_t)(u - own_c) + (ib - eb * C) + p.rg_row_base,
+                    rg_off0 + (uint64_t)(rg_tb + dt) * p.rg_step, p.rg_seed, w0, w1);
+            const float target = u24((i & 64u) ? w1 : w0) * sTab[64];
+            // the count in two levels as k_acc_common_fill4: the block of 8 sums, then that block's sums
+            int nb = 0;
+#pragma unroll
+            for (int b = 0; b < 3; b++) nb += sTab[8 * b + 7] <= target ? 1 : 0;
+            const f4 lo = *reinterpret_cast<const f4*>(sTab + 8 * nb), hi = *reinterpret_cast<const f4*>(sTab + 8 * nb + 4);
+            const int cnt = 8 * nb + (lo[0] <= target) + (lo[1] <= target) + (lo[2] <= target) + (lo[3] <= target) +
+                            (hi[0] <= target) + (hi[1] <= target) + (hi[2] <= target) + (hi[3] <= target);
+            act = cnt >= A ? __float_as_int(sTab[65]) : cnt;
+            olp = sTab[32 + act];
+        };
         auto load_slot = [&](int k, int r0, int lim) {
             if constexpr (MODE == kCommonRow)
                 cs.load_into(sc[k], [&](int q) { return row_src(r0 + q < lim ? r0 + q : rb); }, lane);
@@ -1053,14 +1107,37 @@ __global__ void __launch_bounds__((64 * GradLds<NQ, NT, MODEX>::WPB), ((NQ * NT 
             const uint32_t rel = (uint32_t)((r < lim ? r : rb) - rb);
             if constexpr (MODE == kOwnerRow)
                 s_own[k] = (int8_t)__builtin_amdgcn_raw_buffer_load_b8(ob, (int)__umul24(rel, p.owner_C), 0, 0);
-            s_act[k] = (int8_t)__builtin_amdgcn_raw_buffer_load_b8(wb.ac, (int)__umul24(rel, ac_rb), 0, 0);
-            s_olp[k] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(wb.lp, (int)__umul24(rel, lp_rb), 0, 0));
+            if constexpr (RG) {  // (a common row's by-core pair is loaded too and dropped: no load waits for the owner)
+                rg_load(rel, s_act[k], s_olp[k]);
+            } else {
+                s_act[k] = (int8_t)__builtin_amdgcn_raw_buffer_load_b8(wb.ac, (int)__umul24(rel, ac_rb), 0, 0);
+                s_olp[k] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(wb.lp, (int)__umul24(rel, lp_rb), 0, 0));
+            }
             s_G[k] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(wb.rt, (int)__umul24(rel, rt_rb), 0, 0));
         };
         // the listed rows t0 .. t0 + 16*n - 1 (the last tile may be partial: cnt rows in all) in
         // 16-row tiles, the next tile's rows prefetched
         auto owner_tiles = [&](int cnt) {
-            auto pf = [&](int t0) { prefetch_rel(wb, (uint32_t)(list[t0 + (t0 + j < cnt ? j : 0)] - rb)); };
+            auto pf = [&](int t0) {
+                const int ent = list[t0 + (t0 + j < cnt ? j : 0)];
+                if constexpr (RG) {
+                    // bit 31: a common row the scan could not sum (its term too large): regenerated again
+                    const int r = ent & 0x7fffffff;
+                    const uint32_t rel = (uint32_t)(r - rb);
+#pragma unroll
+                    for (int s = 0; s < S1; s++)
+#pragma unroll
+                        for (int h = 0; h < 2; h++)
+                            pre[s][h] = __builtin_amdgcn_raw_buffer_load_b32(wb.st, (int)(__umul24(rel, st_rb) + ccol[s][h]), 0, 0);
+                    rg_load(rel, pre_act, pre_olp);
+                    pre_G = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(wb.rt, (int)__umul24(rel, rt_rb), 0, 0));
+                    if (__ballot(ent < 0) != 0ull) {
+                        if (ent < 0) regen(r, pre_act, pre_olp);
+                    }
+                } else {
+                    prefetch_rel(wb, (uint32_t)(ent - rb));
+                }
+            };
             pf(0);
             for (int t0 = 0; t0 < cnt; t0 += 16) {
                 uint32_t xr[S1][2];
@@ -1092,9 +1169,16 @@ __global__ void __launch_bounds__((64 * GradLds<NQ, NT, MODEX>::WPB), ((NQ * NT 
                         common = s_own[k] != own_me && in;
                     else
                         common = cs.common_of(sc[k], lane) && in;
-                    const int act = s_act[k];
-                    const float olp = s_olp[k], G = s_G[k];
+                    int act = s_act[k];
+                    float olp = s_olp[k];
+                    const float G = s_G[k];
                     if (r0 + 64 * PF < seg_end) load_slot(k, r0 + 64 * PF, seg_end);
+                    const bool regen_row = RG && common && r >= rg_r0;
+                    if constexpr (RG) {
+                        if (__ballot(regen_row) != 0ull) {
+                            if (regen_row) regen(r, act, olp);
+                        }
+                    }
                     float qd = 0.f, sur1 = 0.f, sur2 = 0.f;
                     if (common) {
                         // the tile path's per-row derivatives with the common row's forward values
@@ -1125,7 +1209,7 @@ __global__ void __launch_bounds__((64 * GradLds<NQ, NT, MODEX>::WPB), ((NQ * NT 
 #ifdef MS_GRAD_PROBE
                     probe_listed += __popcll(m);
 #endif
-                    if (other) list[n_list + __popcll(m & below)] = r;
+                    if (other) list[n_list + __popcll(m & below)] = regen_row ? (int)(0x80000000u | (uint32_t)r) : r;
                     n_list += __popcll(m);
                 }
             }
@@ -1835,6 +1919,10 @@ static hipError_t launch_grad_t(const PpoArgs& a0, hipStream_t st) {
             using L = GradLds<NQ, NT, kCommonRow>;
             if (sizeof(float) * L::lds_floats <= 160 * 1024) {
                 if (a.owner && a.own_mask && a.G >= kOwnMinGroups) return launch_own<NQ, NT, X>(a, nb, st);
+                if (a.owner && a.rg_tab) {  // (tables of FragLayout<2, 2>: rows of 33..64 bytes, 17..32 actions)
+                    if constexpr (NQ == 4 && NT == 2) return launch_grad_cm<NQ, NT, kOwnerRow | kRegen | X>(a, nb, st);
+                    return hipErrorInvalidValue;
+                }
                 if (a.owner) return launch_grad_cm<NQ, NT, kOwnerRow | X>(a, nb, st);
                 return launch_grad_cm<NQ, NT, kCommonRow | X>(a, nb, st);
             }

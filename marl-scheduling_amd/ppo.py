@@ -635,11 +635,16 @@ class PPOGroup:
         return losses
 
     def fused_epoch(self, states_i8, actions_i8, old_logprobs, returns_teg, unit_of_group, T: int, E: int,
-                    stream=None, common_row=None, returns_ld: int = 0, core_owner=None, unit_major: bool = False):
+                    stream=None, common_row=None, returns_ld: int = 0, core_owner=None, unit_major: bool = False,
+                    regen: dict | None = None):
         """The gradient half of one K-epoch step of ``update_fused``, for callers that all-reduce
         several groups' gradients in one call (Trainer.update): returns a function that writes this
         epoch's gradient into ``policy``'s .grad tensors (ms_ppo_grad) and returns the per-group loss
-        (the Adam step is ``hip_optimizer.step``)."""
+        (the Adam step is ``hip_optimizer.step``).
+        regen (with core_owner; ms_ppo_batch's ABI 20 fields): dict(frag=the acceptor's ActFrag buffer as it was
+        at acting time, own_action / own_logprob [R, C], seed, offset (ring slot 0's acting offset), offset_dev,
+        offset_step, row_base, slot0): from ring slot slot0 on the kernel regenerates the common rows' actions and
+        old log-probs and reads the own rows' by core, instead of reading actions_i8 / old_logprobs."""
         pol = self.policy
         # compact acceptor rows (core_owner [R, C]): states are the core rows [R, C, stride], and U
         # (= N*C units) comes from the actions
@@ -664,10 +669,20 @@ class PPOGroup:
         batch = abi.MsPpoBatch(ptr(states_i8), ptr(actions_i8), ptr(old_logprobs), ptr(returns_teg),
                                ptr(unit_of_group), stride, T, U, E, ptr(common_row), int(returns_ld),
                                ptr(core_owner), n_cores, int(getattr(self, "row_keys", 0)), R if unit_major else 0)
+        if regen is not None:
+            oa, ol = regen["own_action"], regen["own_logprob"]
+            assert core_owner is not None and oa.shape == (R, n_cores) and ol.shape == (R, n_cores)
+            assert oa.dtype == torch.int8 and ol.dtype == torch.float32 and oa.is_contiguous() and ol.is_contiguous()
+            batch.regen_frag, batch.own_action, batch.own_logprob = ptr(regen["frag"]), ptr(oa), ptr(ol)
+            batch.regen_seed, batch.regen_offset = int(regen["seed"]), int(regen["offset"])
+            batch.regen_offset_dev = ptr(regen.get("offset_dev"))
+            batch.regen_offset_step, batch.regen_row_base = int(regen["offset_step"]), int(regen.get("row_base", 0))
+            batch.regen_slot0 = int(regen["slot0"])
         grads = abi.MsPpoGrads(*[ptr(getattr(pol, k).grad) for k in ACTOR_KEYS + CRITIC_KEYS], ptr(loss_buf))
         # the structs above hold raw device pointers: the closure keeps every tensor they point into
         # alive until its last launch (a caller's temporaries would otherwise be freed and reused)
-        keep = (states_i8, actions_i8, old_logprobs, returns_teg, unit_of_group, common_row, core_owner, ws, loss_buf)
+        keep = (states_i8, actions_i8, old_logprobs, returns_teg, unit_of_group, common_row, core_owner, ws, loss_buf,
+                regen)
 
         def launch(out=None):
             """The gradient; the loss terms [G][3] into out (a caller's [G][3] float32 tensor, e.g. one epoch's

@@ -30,7 +30,7 @@ import numpy as np
 import torch
 
 from . import abi
-from ._lib import ABI_LOADED, hip_capture, ptr
+from ._lib import ABI_LOADED, capturing, hip_capture, ptr
 from .env import BatchedEnv
 from .ppo import (ActFrag, PPOGroup, PriceTable, act_round_free, act_round_greedy, combine_losses, discounted_returns,
                   offer_act_free, reference_init_order, reference_nets, unit_returns)
@@ -65,15 +65,31 @@ class _Unit:
         # unit_major: actions / log-probs stored [U][T][E] (one unit's rows of every replica are
         # contiguous for the update's gathers); .actions / .logprobs stay [T][E][U] views
         self.unit_major = unit_major
+        # actions_raw / logprobs_raw: the ring tensors as they are (the kernels' pointers come from these);
+        # .actions / .logprobs first run `complete` (Trainer._complete_rings for the acceptors, whose rings an
+        # iteration() leaves without the items the gradient regenerates), then return the same tensors
+        self.complete = None
         if unit_major:
             self.actions_um = torch.zeros((n_units, T, E), dtype=torch.int8, device=device)
             self.logprobs_um = torch.zeros((n_units, T, E), dtype=torch.float32, device=device)
-            self.actions = self.actions_um.permute(1, 2, 0)
-            self.logprobs = self.logprobs_um.permute(1, 2, 0)
+            self.actions_raw = self.actions_um.permute(1, 2, 0)
+            self.logprobs_raw = self.logprobs_um.permute(1, 2, 0)
         else:
-            self.actions = torch.zeros((T, E, n_units), dtype=torch.int8, device=device)
-            self.logprobs = torch.zeros((T, E, n_units), dtype=torch.float32, device=device)
+            self.actions_raw = torch.zeros((T, E, n_units), dtype=torch.int8, device=device)
+            self.logprobs_raw = torch.zeros((T, E, n_units), dtype=torch.float32, device=device)
         self.rewards = torch.zeros((T, E, n_units), dtype=reward_dtype, device=device)
+
+    @property
+    def actions(self):
+        if self.complete is not None:
+            self.complete()
+        return self.actions_raw
+
+    @property
+    def logprobs(self):
+        if self.complete is not None:
+            self.complete()
+        return self.logprobs_raw
 
     def batch(self, states_i8, u_sel):
         """Gather the update batch of the selected unit per group (u_sel [G] long)."""
@@ -310,6 +326,18 @@ class Trainer:
         if self.fused_rollout_free and ABI_LOADED >= 18 and os.environ.get("MS_FILL_OWN", "1") != "0":
             self.acc_own = (torch.zeros((T, self.E, C), dtype=torch.int8, device=dev),
                             torch.zeros((T, self.E, C), dtype=torch.float32, device=dev))
+        # the acceptor gradient regenerates the items the fill would write (ms_ppo_batch's regen fields, ABI 20):
+        # the rollout always leaves them, iteration() never runs the fill, and whoever reads the acceptor rings
+        # afterwards (acc.actions / acc.logprobs) gets them completed by one eager fill (_complete_rings).
+        # One replica part only (the fill's arguments and the row base are one part's); any world size.
+        # MS_ACC_REGEN=0: the fill after the rollout and a gradient that reads the rings (A/B runs, equality tests);
+        # so does MS_DEFER_COMMON=1 (the fill moved into the update, where the gradient then reads the rings)
+        self.acc_regen = (self.fused_rollout_free and self.acc_own is not None and self.fused and
+                          rollout_streams == 1 and ABI_LOADED >= 20 and not self.defer_common and
+                          os.environ.get("MS_ACC_REGEN", "1") != "0")
+        if self.acc_regen:
+            self.acc.complete = self._complete_rings
+        self._rings_pending = False
         self._fill_args = []
         self.span_every = 0  # > 0: every span_every-th round's env launches record their span (bench)
         self.spans = None
@@ -357,6 +385,7 @@ class Trainer:
         possible inputs and the act weight fragments (ms_act_prepare). They are rebuilt at the start
         of every rollout (inside the rollout graph) and by round() after an update changed
         policy_old (sync_old bumps _policy_version)."""
+        self._complete_rings()  # a pending fill samples from the tables about to be rebuilt
         if self.price_table is not None:
             self.price_table.build(self.price.group.policy_old)
         if self.off_frag is not None:
@@ -532,18 +561,38 @@ class Trainer:
         if self.acc_own is not None:
             strides.next_own_action, strides.next_own_logprob = b(self.acc_own[0]), b(self.acc_own[1])
         nxt, out = self._fused_next_free(1, k)
-        nxt.defer_common = int(self.defer_common)
+        nxt.defer_common = int(self.defer_common or self.acc_regen)
         env.rollout_act_free(sl(self.acc.actions[0]).view(E, N, C), sl(self.off.actions[0]).view(E, N, L), obs, rew,
                              nxt, out, strides, self.T, act_after_last=False, events=ev, stream=self.streams[k])
-        if self.defer_common:  # the fill's arguments: the same call with the offsets of this rollout (snapshot)
+        if self.defer_common or self.acc_regen:
+            # the fill's arguments: the same call with the offsets of this rollout (snapshot). It reads the owners
+            # of ring slots >= 1 (_carry_last_observation rewrites slot 0 only) and the acceptor tables of
+            # this rollout (_prepare_acting completes pending rings before it rebuilds them)
+            assert obs["core_owner"].data_ptr() == self.acc_owner[1][e0:e1].data_ptr() and self.T > 1
             fill = abi.MsFusedActFree.from_buffer_copy(nxt)
             fill.offset_dev = ptr(self.rng_snap)
             self._fill_args.append((env, obs, fill, strides))
 
     def fill_common(self, stream=None):
-        """The deferred acceptor items of the last one-launch rollout (defer_common; idempotent)."""
+        """The deferred acceptor items of the last one-launch rollout (defer_common / acc_regen; idempotent)."""
         for env, obs, fill, strides in self._fill_args:
             env.fill_common(obs, fill, strides, self.T, act_after_last=False, stream=stream)
+
+    def _complete_rings(self):
+        """The acceptor rings' items an iteration() left to the gradient's regeneration (acc_regen): one eager
+        fill on the current stream at the first read after the rollout, never inside a capture."""
+        if self._rings_pending and not capturing():
+            self._rings_pending = False
+            self.fill_common()
+
+    def _acc_regen_args(self):
+        """ms_ppo_batch's regen fields for the acceptor epochs (PPOGroup.fused_epoch): ring slot t of the last
+        rollout acted with offset 8 t + 3 + the counter the rollout snapshot (_act_part / _fused_next_free), from
+        the tables acc_frag holds until the next rollout rebuilds them; slot 0 (ms_act_round_free) is read."""
+        T, E, C = self.T, self.E, self.C
+        return dict(frag=self.acc_frag.buf, own_action=self.acc_own[0].view(T * E, C),
+                    own_logprob=self.acc_own[1].view(T * E, C), seed=self.seed * 7919, offset=3, offset_step=8,
+                    offset_dev=self.rng_snap, row_base=self.rank * self.E * self.N * C, slot0=1)
 
     def record_launch_spans(self, every: int):
         """Every `every`-th round's env launches record their span (first wave start, last wave end
@@ -591,7 +640,7 @@ class Trainer:
             self.spans.zero_()
         self._prepare_acting()
         self._fill_args = []
-        if self.defer_common:
+        if self.defer_common or self.acc_regen:
             self.rng_snap.copy_(self.rng_ctr)
         for s in self.streams[1:]:  # fork: the side streams start after everything queued so far
             s.wait_stream(cur)
@@ -611,6 +660,7 @@ class Trainer:
         captured once into a HIP graph (every pointer is static); later rollouts replay it.
         defer_common (iteration()): leave the deferred acceptor items (self.defer_common) to the update, which
         samples them on the acceptor's stream; otherwise the rings are complete when this returns."""
+        self._rings_pending = False  # (rings of an earlier rollout nobody read: overwritten now)
         if not self.use_graph:
             self._rollout_body()
         elif self.graph is None:
@@ -622,7 +672,11 @@ class Trainer:
             self.graph = g
         else:
             self.graph.replay()
-        if self.defer_common and not defer_common:
+        if self.acc_regen:
+            self._rings_pending = True
+            if not defer_common:
+                self._complete_rings()
+        elif self.defer_common and not defer_common:
             self.fill_common()
         self.rounds_done += self.T
 
@@ -680,8 +734,8 @@ class Trainer:
         if u.unit_major:
             st = self.price_obs_um if u is self.price else None
             return st.reshape(u.U, T * E, u.stride), u.actions_um.reshape(u.U, T * E), u.logprobs_um.reshape(u.U, T * E)
-        return (self._states_of(u).reshape(T * E, -1, u.stride), u.actions.view(T * E, u.U),
-                u.logprobs.view(T * E, u.U))
+        return (self._states_of(u).reshape(T * E, -1, u.stride), u.actions_raw.view(T * E, u.U),
+                u.logprobs_raw.view(T * E, u.U))
 
     def _states_of(self, u):
         T = self.T
@@ -788,11 +842,13 @@ class Trainer:
             ret_all = unit_returns(u.rewards, sel_u, u.group.gamma)
             common = self.acc_common if (u is self.acc and self.common_rows) else None
             owner = self.acc_owner[:T].reshape(T * E, self.C) if (u is self.acc and self.compact) else None
+            regen = self._acc_regen_args() if (u is self.acc and self.acc_regen) else None
             col, seq = 0, []
             rows = self._update_rows(u)
             for n in counts[u.name]:
                 ep = u.group.fused_epoch(*rows, ret_all.view(-1)[col:], sel_u[col:col + n], T, E, common_row=common,
-                                         returns_ld=sel_u.numel(), core_owner=owner, unit_major=u.unit_major)
+                                         returns_ld=sel_u.numel(), core_owner=owner, unit_major=u.unit_major,
+                                         regen=regen)
                 seq += [ep] * u.group.K
                 col += n
             steps[u.name] = (u, seq, [])
@@ -822,11 +878,12 @@ class Trainer:
         ret_all = unit_returns(u.rewards, sel_u, u.group.gamma)
         common = self.acc_common if (u is self.acc and self.common_rows) else None
         owner = self.acc_owner[:T].reshape(T * E, self.C) if (u is self.acc and self.compact) else None
+        regen = self._acc_regen_args() if (u is self.acc and self.acc_regen) else None
         rows = self._update_rows(u)
         col, seq = 0, []
         for n in counts_u:
             ep = u.group.fused_epoch(*rows, ret_all.view(-1)[col:], sel_u[col:col + n], T, E, common_row=common,
-                                     returns_ld=sel_u.numel(), core_owner=owner, unit_major=u.unit_major)
+                                     returns_ld=sel_u.numel(), core_owner=owner, unit_major=u.unit_major, regen=regen)
             seq += [ep] * u.group.K
             col += n
         return seq
