@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define MS_ABI_VERSION 20
+#define MS_ABI_VERSION 21
 
 #define MS_MAX_KINDS 16
 #define MS_MAX_AGENTS 64
@@ -175,7 +175,10 @@ typedef struct ms_term_rec {
  * trainDQN.py:187-259): every ms_env_step that is given them adds its round into the slot of the
  * round's episode. The caller reads a slot once its episode is done (world.round % episodeLength
  * == 0, SchedulingEnvironment.py:64-67) and zeroes it before the slot is reused. Updated with
- * no-return device atomics, one env per group of lanes, so the order per replica is fixed. */
+ * no-return device atomics, one env per group of lanes, so the order per replica is fixed; inside
+ * the launches of several rounds (ABI 21: ms_env_rollout_act, ms_env_rollout_act_free) quality_sum,
+ * whose terms are inexact, is added round after round by one lane's ordered read-modify-write, so
+ * the accumulators equal those of the same rounds through ms_env_step bit for bit. */
 typedef struct ms_env_metrics {
     int64_t acceptor_reward;     /* sum over rounds and units of acceptorNetRewards */
     int64_t offer_reward;        /* sum of offerNetRewards / coreChooserRewards (prio1, integers) */
@@ -435,6 +438,7 @@ typedef struct ms_fused_act {
 } ms_fused_act;
 
 /* ms_env_step followed by the fused acting of `next` (obs must hold core_rows / core_owner and offer).
+ * ev->metrics (ABI 21) is accumulated as by ms_env_step, bit for bit.
  * MS_EINVAL when the shapes are not supported (the caller then steps and acts in two calls). */
 int ms_env_step_act(ms_env* env, const ms_actions* act, const ms_obs_out* obs, const ms_reward_out* rew,
                     const ms_event_out* ev, const ms_fused_act* next, void* stream);
@@ -459,7 +463,10 @@ typedef struct ms_round_strides {
  * wrote, with no launch between rounds. The acting after the last round runs only when
  * act_after_last != 0. ev->launch_span (optional) records the whole launch ([waves][4]). Outputs
  * are bit-identical to the n_rounds separate calls. Same requirements as ms_env_step_act, plus
- * no accepted / terminated event records and no price / aggregated reward outputs. */
+ * no accepted / terminated event records and no price / aggregated reward outputs. ev->metrics
+ * (ABI 21; metrics_slots >= 1, the one array for every round, not strided) receives every round's
+ * episode metrics, each round in the slot of its own episode: the accumulators equal those of
+ * n_rounds ms_env_step calls bit for bit, the two doubles included. */
 int ms_env_rollout_act(ms_env* env, const ms_actions* act, const ms_obs_out* obs, const ms_reward_out* rew,
                        const ms_event_out* ev, const ms_fused_act* next, const ms_round_strides* strides,
                        int32_t n_rounds, int32_t act_after_last, void* stream);
@@ -515,9 +522,11 @@ typedef struct ms_round_strides_free {
  * acting refills), writes obs / rewards advanced by t strides, and then (t < n_rounds - 1, or act_after_last)
  * samples round t + 1's actions into next's outputs advanced by t strides, with offsets + t * offset_step.
  * Bit-identical to n_rounds pairs of ms_env_step + ms_act_round_free. Requires free prices, compact acceptor
- * observations (core_rows, core_owner, offer), no events or metrics or aggregated rewards,
+ * observations (core_rows, core_owner, offer), no accepted / terminated event records or aggregated rewards,
  * ms_env_rollout_act_free_supported, N groups per net, act fragments for both nets and a price table.
- * Every ring must hold n_rounds slots at its stride (the kernel does not see the sizes). MS_EINVAL otherwise. */
+ * Every ring must hold n_rounds slots at its stride (the kernel does not see the sizes). MS_EINVAL otherwise.
+ * ev->metrics (ABI 21; metrics_slots >= 1, not strided) receives every round's episode metrics in the slot of
+ * the round's own episode, equal to those of n_rounds ms_env_step calls bit for bit. */
 int ms_env_rollout_act_free(ms_env* env, const ms_actions* act, const ms_obs_out* obs, const ms_reward_out* rew,
                             const ms_event_out* ev, const ms_fused_act_free* next, const ms_round_strides_free* strides,
                             int32_t n_rounds, int32_t act_after_last, void* stream);

@@ -27,7 +27,7 @@ class MarlSchedError(RuntimeError):
         self.code = code
 
 
-ABI_VERSION = 20  # include/marlsched.h MS_ABI_VERSION
+ABI_VERSION = 21  # include/marlsched.h MS_ABI_VERSION
 
 
 def _load():
@@ -132,9 +132,11 @@ def _load():
     # ms_env_rollout_act, 17 ms_env_rollout_act_free, 18 its own_action / own_logprob (trailing fields a 17
     # library does not read: it writes the owned items into the rings itself), 19 the greedy acting entry points
     # (ms_policy_act_greedy, ms_act_round_greedy), 20 ms_ppo_batch's regen fields (trailing fields an older library
-    # does not read: the trainer passes them from ABI 20 on only). An older library (an A/B variant built before them,
+    # does not read: the trainer passes them from ABI 20 on only), 21 episode metrics inside ms_env_step_act /
+    # ms_env_rollout_act / ms_env_rollout_act_free (an older library refuses them: the trainer then keeps the
+    # launch-per-round path under metrics). An older library (an A/B variant built before them,
     # tools/gpu_job.sh ab step) loads without them only when MARLSCHED_LENIENT_ABI=1 asks for it
-    lenient = os.environ.get("MARLSCHED_LENIENT_ABI") == "1" and version in (13, 14, 15, 16, 17, 18, 19, 20)
+    lenient = os.environ.get("MARLSCHED_LENIENT_ABI") == "1" and version in (13, 14, 15, 16, 17, 18, 19, 20, 21)
     if version != ABI_VERSION and not lenient:
         raise ImportError("libmarlsched.so ABI version mismatch (%d, want %d)" % (version, ABI_VERSION))
     for name, (res, args) in sig.items():

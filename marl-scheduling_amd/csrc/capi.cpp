@@ -280,7 +280,7 @@ static int fused_act_args(ms_env* env, const ms_actions* act, const ms_obs_out* 
     if (env->cfg.free_prices) return bad("fixed-price rounds only");
     if (!obs || !obs->core_rows || !obs->core_owner || !obs->offer || obs->acceptor)
         return bad("needs compact acceptor observations (core_rows, core_owner) and offer rows");
-    if (!act || !act->acceptor || (ev && ev->metrics)) return bad("the trainer's round only (actions given, no metrics)");
+    if (!act || !act->acceptor) return bad("the trainer's round only (actions given)");
     const ms_mlp_params& o = next->offer;
     const ms_mlp_params& a = next->acceptor;
     if (o.n_groups != 1 || a.n_groups != 1 || o.hidden != 16 || a.hidden != 16 || !o.act_frag || !a.act_frag)
@@ -428,7 +428,7 @@ int ms_env_rollout_act_free(ms_env* env, const ms_actions* act, const ms_obs_out
         return bad("needs compact acceptor observations (core_rows, core_owner) and offer rows only");
     if (!act->acceptor || !act->offer_core || act->offer_price != next->env_price || act->auctioneer)
         return bad("actions: acceptor and offer_core given, offer_price = next->env_price, no auctioneer actions");
-    if (ev && (ev->accepted || ev->terminated || ev->metrics)) return bad("no event records or metrics");
+    if (ev && (ev->accepted || ev->terminated)) return bad("no accepted / terminated event records");
     if (rew && (rew->aggregated_offer || rew->aggregated_acceptor)) return bad("no aggregated reward outputs");
     const ms_mlp_params& c = next->core_chooser;
     const ms_mlp_params& p = next->price_chooser;

@@ -460,6 +460,20 @@ __device__ __forceinline__ void m_add(int64_t* p, long long v) {
 __device__ __forceinline__ void m_add(double* p, double v) {
     if (v != 0.0) unsafeAtomicAdd(p, v);
 }
+// quality_sum inside a launch of several rounds (MET rounds of the fused kernels): its terms are not exactly
+// representable, so the sum depends on the order of the adds, and nothing orders two no-return float atomics
+// of successive rounds. Only the replica's group leader touches the field, so that one lane reads it, adds and
+// writes it back: relaxed agent-scope accesses (served by the L2, where ms_env_step's atomics land) of one
+// thread to one address stay in program order, round after round, and the add rounds as the L2's atomic does.
+// The load is issued before the executions and its wait falls behind them. (price_reward stays an atomic: its
+// terms are float sums of integers and net_zero, multiples of 2^-27 or coarser, exact in a double in any order
+// up to 2^26. The integer fields are order-free.)
+__device__ __forceinline__ double m_load(const double* p) {
+    return __hip_atomic_load(const_cast<double*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ void m_store(double* p, double v) {
+    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
 
 // Masks of the current offers: mc[c] = offers to core c, mr[r] = offers to
 // recipient r (0 = auctioneer). Ends with a phase boundary.
@@ -1009,8 +1023,11 @@ constexpr int kLiabPrefetch = 4;  // newest chain entries loaded ahead per core 
 // compact acceptor observations); the plain training round is compiled without them, so it carries
 // none of their registers (the compact emission beside the full rows costs ~90 spilled SGPRs). CMP:
 // the plain round that emits the compact acceptor observations instead of the [N][C] rows (the
-// training loop's form: its act and gradient kernels read core rows + owners).
-template <int LPE, bool EXT, bool CMP, class SH>
+// training loop's form: its act and gradient kernels read core rows + owners). MET: the episode metrics alone
+// (the m_add sites and the rank-ordered executions they need) on a plain round, for the fused kernels given
+// io.metrics: none of EXT's hard-coded agents, full acceptor rows or generic shape. SEQ: the round is one of
+// several in its launch, so quality_sum is added by the leader's ordered read-modify-write (m_load / m_store).
+template <int LPE, bool EXT, bool CMP, class SH, bool MET = EXT, bool SEQ = false>
 __device__ __forceinline__ void env_round(const Params& P, int64_t E, uint8_t* recs, uint32_t* mt, Liab* liab,
                                           const StepIO& io, int64_t slot, int lane_arg = -1,
                                           uint8_t* wave_lds = nullptr, const int8_t* acc_lds = nullptr) {
@@ -1147,7 +1164,7 @@ __device__ __forceinline__ void env_round(const Params& P, int64_t E, uint8_t* r
     Liab* my_liab = liab + e * (int64_t)C * P.cap;
     // this round's episode accumulators (trainPPO.py:172-187): slot of episode round / episodeLength
     const bool HC = EXT && io.act_acc == nullptr;
-    constexpr bool MX = EXT;
+    constexpr bool MX = MET;
     ms_env_metrics* mx = (MX && io.metrics && active)
                              ? io.metrics + (int64_t)((round / P.ep_len) % io.metrics_slots) * E + e
                              : nullptr;
@@ -1233,7 +1250,7 @@ __device__ __forceinline__ void env_round(const Params& P, int64_t E, uint8_t* r
     //      removals and insertions of every collection, in rank order, on the collection owner's
     //      lane. With episode metrics or event records (their rank-ordered sums) the groups' leaders
     //      run the executions one after another instead.
-    if (!EXT && io.ev_acc == nullptr) {
+    if (!EXT && !MX && io.ev_acc == nullptr) {
         // per core, in the scratch (free between the staging and the observation emission): the
         // job its execution dispatched away (for the insertion), the offerer and the recipient
         int32_t* x_birth = reinterpret_cast<int32_t*>(scratch);
@@ -1314,6 +1331,9 @@ __device__ __forceinline__ void env_round(const Params& P, int64_t E, uint8_t* r
         }
     } else if (gl == 0) {
         const int n_exec = s_n_exec;
+        double q_old = 0.0;
+        if constexpr (MX && SEQ)
+            if (mx) q_old = m_load(&mx->quality_sum);
         double q_sum = 0.0;  // calculateAverageAcceptionQuality (SchedulingEnvironment.py:174-192)
         int n_q = 0;
         for (int r = 0; r < n_exec; r++) {
@@ -1405,7 +1425,12 @@ __device__ __forceinline__ void env_round(const Params& P, int64_t E, uint8_t* r
             }
         }
         if (MX && mx && n_q > 0) {  // statistics.mean of the round's qualities, then collected per round
-            m_add(&mx->quality_sum, q_sum / n_q);
+            const double q_mean = q_sum / n_q;
+            if constexpr (SEQ) {
+                if (q_mean != 0.0) m_store(&mx->quality_sum, q_old + q_mean);  // (m_add skips a zero term too)
+            } else {
+                m_add(&mx->quality_sum, q_mean);
+            }
             m_add(&mx->quality_rounds, 1);
             m_add(&mx->acception_amount, n_q);
         }
@@ -1847,15 +1872,16 @@ __global__ void __launch_bounds__(64, 4) k_env_step(Params P, int64_t E, uint8_t
 #endif
 }
 
-// the round of k_env_step (compact acceptor observations) and then the next round's acting (fused_act)
-template <int LPE, class SH>
+// the round of k_env_step (compact acceptor observations) and then the next round's acting (fused_act);
+// MET: the round with the episode metrics (io.metrics given; env_round)
+template <int LPE, class SH, bool MET = false>
 __global__ void __launch_bounds__(64, 4) k_env_step_act(Params P, int64_t E, uint8_t* recs, uint32_t* mt, Liab* liab,
                                                      StepIO io, FusedAct fa) {
     if (io.span && threadIdx.x == 0) {
         io.span[4 * blockIdx.x] = __builtin_amdgcn_s_memrealtime();
         io.span[4 * blockIdx.x + 2] = __builtin_amdgcn_s_memtime();
     }
-    env_round<LPE, false, true, SH>(P, E, recs, mt, liab, io, blockIdx.x);
+    env_round<LPE, false, true, SH, MET>(P, E, recs, mt, liab, io, blockIdx.x);
     fused_act<LPE, SH>(P, E, fa, blockIdx.x);
     if (io.span && threadIdx.x == 0) {
         io.span[4 * blockIdx.x + 3] = __builtin_amdgcn_s_memtime();
@@ -1885,7 +1911,8 @@ struct RolloutArgs {
     RoundStride st;
     int n_rounds, act_last;
 };
-template <int LPE, class SH>
+// MET: every round adds its episode metrics (the slot follows the round's own episode; io.metrics is not strided)
+template <int LPE, class SH, bool MET = false>
 __global__ void __launch_bounds__(64, 2) k_env_rollout_act(RolloutArgs A0) {
     unsigned long long* span = A0.io.span;
     if (span && threadIdx.x == 0) {
@@ -1911,7 +1938,7 @@ __global__ void __launch_bounds__(64, 2) k_env_rollout_act(RolloutArgs A0) {
         io.rew_acc = advance(io.rew_acc, t * st.rew_acc);
         io.rew_agent = advance(io.rew_agent, t * st.rew_agent);
         io.rew_auct = advance(io.rew_auct, t * st.rew_auct);
-        env_round<LPE, false, true, SH>(A.P, A.E, A.recs, A.mt, A.liab, io, blockIdx.x, lane);
+        env_round<LPE, false, true, SH, MET, MET>(A.P, A.E, A.recs, A.mt, A.liab, io, blockIdx.x, lane);
         if (t + 1 < n_rounds || A.act_last) {
             FusedAct fa = A.fa;
             fa.off_action = advance(fa.off_action, t * st.off_action);
@@ -2529,7 +2556,8 @@ struct RolloutFreeArgs {
 // act from registers and LDS on the rows the round just built, instead of an act launch re-reading them from
 // HBM. Round t's arrays are the given ones advanced by t strides. The round re-reads its arguments through
 // the opaque kernel-argument pointer (k_env_rollout_act). Two workgroups per CU: 4 waves per SIMD (<= 128 VGPRs).
-template <class SH>
+// MET: every round adds its episode metrics (env_round; the padding groups of a partial last workgroup add nothing).
+template <class SH, bool MET = false>
 __global__ void __launch_bounds__(512, 4) k_env_rollout_act_free(RolloutFreeArgs A0) {
     extern __shared__ __align__(16) uint8_t smem_free[];
     Geom g;
@@ -2606,8 +2634,8 @@ __global__ void __launch_bounds__(512, 4) k_env_rollout_act_free(RolloutFreeArgs
         const int8_t* acc_lds = t > 0 && A.fa.own_action
                                     ? reinterpret_cast<const int8_t*>(smem_free + fl.accx) + wave * kFreeEPW * g.N * g.C
                                     : nullptr;
-        env_round<kWave / kFreeEPW, false, true, SH>(A.P, A.E, A.recs, A.mt, A.liab, io, wslot, lane,
-                                                     smem_free + wave * free_slot(g), acc_lds);
+        env_round<kWave / kFreeEPW, false, true, SH, MET, MET>(A.P, A.E, A.recs, A.mt, A.liab, io, wslot, lane,
+                                                               smem_free + wave * free_slot(g), acc_lds);
         if (up) __builtin_amdgcn_s_setprio(0);
         FREE_MARK(0);
         if (t + 1 < n_rounds || A.act_last) {
@@ -2850,14 +2878,13 @@ static hipError_t launch_step_act_sh(const Params& P, int64_t E, uint8_t* recs, 
     constexpr int G = kWave / LPE;
     const int64_t blocks = (E + G - 1) / G;
     const size_t lds = (size_t)P.s_total * G > 4 * kMtN ? (size_t)P.s_total * G : 4 * kMtN;
-    hipLaunchKernelGGL((k_env_step_act<LPE, SH>), dim3((unsigned)blocks), dim3(kWave), lds, s, P, E, recs, mt, liab, io,
-                       fa);
+    auto kern = io.metrics ? k_env_step_act<LPE, SH, true> : k_env_step_act<LPE, SH, false>;
+    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(kWave), lds, s, P, E, recs, mt, liab, io, fa);
     return hipGetLastError();
 }
 hipError_t launch_env_step_act(const Params& P, int64_t E, uint8_t* recs, uint32_t* mt, Liab* liab, const StepIO& io,
                                const FusedAct& fa, hipStream_t s) {
-    if (!env_step_act_supported(P, E) || io.act_acc == nullptr || io.metrics != nullptr || io.obs_acc != nullptr)
-        return hipErrorInvalidValue;
+    if (!env_step_act_supported(P, E) || io.act_acc == nullptr || io.obs_acc != nullptr) return hipErrorInvalidValue;
     switch (lanes_per_env(P, E)) {
         case 16: return launch_step_act_sh<16, DynShape>(P, E, recs, mt, liab, io, fa, s);
         case 32:
@@ -2876,14 +2903,15 @@ static hipError_t launch_rollout_act_sh(const Params& P, int64_t E, uint8_t* rec
     const int64_t blocks = (E + G - 1) / G;
     const size_t lds = (size_t)P.s_total * G > 4 * kMtN ? (size_t)P.s_total * G : 4 * kMtN;
     const RolloutArgs A{P, E, recs, mt, liab, io, fa, st, n_rounds, act_last};
-    hipLaunchKernelGGL((k_env_rollout_act<LPE, SH>), dim3((unsigned)blocks), dim3(kWave), lds, s, A);
+    auto kern = io.metrics ? k_env_rollout_act<LPE, SH, true> : k_env_rollout_act<LPE, SH, false>;
+    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(kWave), lds, s, A);
     return hipGetLastError();
 }
 hipError_t launch_env_rollout_act(const Params& P, int64_t E, uint8_t* recs, uint32_t* mt, Liab* liab,
                                   const StepIO& io, const FusedAct& fa, const RoundStride& st, int n_rounds,
                                   int act_last, hipStream_t s) {
-    if (!env_step_act_supported(P, E) || io.act_acc == nullptr || io.metrics != nullptr || io.obs_acc != nullptr ||
-        n_rounds < 1)
+    if (!env_step_act_supported(P, E) || io.act_acc == nullptr || io.obs_acc != nullptr || io.ev_acc != nullptr ||
+        io.ev_term != nullptr || n_rounds < 1)
         return hipErrorInvalidValue;
     switch (lanes_per_env(P, E)) {
         case 16: return launch_rollout_act_sh<16, DynShape>(P, E, recs, mt, liab, io, fa, st, n_rounds, act_last, s);
@@ -2917,8 +2945,8 @@ static hipError_t launch_rollout_free_sh(const Params& P, int64_t E, uint8_t* re
         return v ? atoi(v) : 4;
     }();
     const RolloutFreeArgs A{P, E, recs, mt, liab, io, fa, st, n_rounds, act_last, prio};
-    hipLaunchKernelGGL((k_env_rollout_act_free<SH>), dim3((unsigned)blocks), dim3(64 * P.N), (size_t)free_lds(P).total, s,
-                       A);
+    auto kern = io.metrics ? k_env_rollout_act_free<SH, true> : k_env_rollout_act_free<SH, false>;
+    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(64 * P.N), (size_t)free_lds(P).total, s, A);
     return hipGetLastError();
 }
 // quads with owned items stored whole, merged with the values the rollout wrote: every line of the outputs is
@@ -2995,8 +3023,8 @@ hipError_t launch_env_fill_common(const Params& P, int64_t E, const StepIO& io, 
 hipError_t launch_env_rollout_act_free(const Params& P, int64_t E, uint8_t* recs, uint32_t* mt, Liab* liab,
                                        const StepIO& io, const FusedActFree& fa, const RoundStrideFree& st,
                                        int n_rounds, int act_last, hipStream_t s) {
-    if (!env_rollout_free_supported(P) || io.act_acc == nullptr || io.metrics != nullptr || io.obs_acc != nullptr ||
-        n_rounds < 1)
+    if (!env_rollout_free_supported(P) || io.act_acc == nullptr || io.obs_acc != nullptr || io.ev_acc != nullptr ||
+        io.ev_term != nullptr || n_rounds < 1)
         return hipErrorInvalidValue;
 #ifndef MS_NO_FIXED_SHAPES
     if (is_shape<8, 8, 3, 1>(P))

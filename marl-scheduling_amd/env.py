@@ -217,7 +217,9 @@ class BatchedEnv:
         writes the given arrays advanced by t * strides (an abi.MsRoundStrides, bytes) and acts with the
         Philox offsets + t * strides.offset_step. Bit-identical to the n_rounds step calls.
         next_out: the tensors behind next_act's outputs, dict(off_action, off_logprob, acc_action, acc_logprob)
-        (round 0's slots), bounds-checked like the other rings when given."""
+        (round 0's slots), bounds-checked like the other rings when given.
+        events: launch_span and / or metrics (a metrics_buffer: every round adds into the slot of its own
+        episode, as n_rounds step calls would, bit for bit; ABI 21); no accepted / terminated records."""
         for t in (acceptor, offer_core):
             assert t.dtype == torch.int8 and t.device == self.device
         rings = self._ring_list(acceptor, offer_core, obs, rewards, strides)
@@ -239,7 +241,8 @@ class BatchedEnv:
         cfg3): round t steps the replicas with the actions advanced by t strides and next_out["env_price"] as the
         offer prices, writes obs / rewards advanced by t strides, then samples round t + 1's actions into next_act's
         outputs (an abi.MsFusedActFree; next_out: its tensors, round 0's slots) advanced by t strides. Bit-identical
-        to n_rounds pairs of step + act_round_free (SchedulingEnvironment.py:150-172, trainPPO.py:160-167)."""
+        to n_rounds pairs of step + act_round_free (SchedulingEnvironment.py:150-172, trainPPO.py:160-167).
+        events: as for rollout_act (launch_span, metrics)."""
         i8, f32 = torch.int8, torch.float32
         assert self.free_prices and next_out["env_price"].numel() == self.E * self.N * self.L
         rings = self._ring_list(acceptor, offer_core, obs, rewards, strides, price=True)

@@ -294,13 +294,18 @@ class Trainer:
         # multi-stream update graph), so it was off. Round 6, with cfg3's rollout one launch: update 8.50 -> 8.05 ms,
         # rollout 9.99 -> 10.11 ms, iteration 18.50 -> 18.18 ms (profiles/r7b), so it is on
         self.update_streams = os.environ.get("MS_UPDATE_STREAMS", "1") == "1"
+        # the fused env launches below add the episode metrics themselves (ABI 21), so metrics=True keeps them
+        # (MS_ROLLOUT_METRICS=0, or an older library: metrics force an act launch and an env launch per round,
+        # for A/B measurements and equality tests)
+        fused_metrics_ok = self.metric_bufs is None or (ABI_LOADED >= 21 and
+                                                        os.environ.get("MS_ROLLOUT_METRICS", "1") != "0")
         # fixed-price rounds with one net per role (cfg2): round t's env launch also samples round t + 1's
         # actions from the observations it just built (ms_env_step_act), so a round is one launch
         # (MS_ENV_FUSED_ACT=0: the act launch and the env launch of every round, for A/B measurements)
         # (T > 1: the fused acting writes round t + 1's ring slots)
         self.fused_step = (self.compact and not self.free and self.acc.group.policy.G == 1 and
                            self.off.group.policy.G == 1 and self.acc_frag is not None and self.T > 1 and
-                           os.environ.get("MS_ENV_FUSED_ACT", "1") != "0" and self.metric_bufs is None and
+                           os.environ.get("MS_ENV_FUSED_ACT", "1") != "0" and fused_metrics_ok and
                            all(env.fused_act_supported() for env, _, _ in self.env.parts))
         # ... and the whole rollout's rounds are one launch (ms_env_rollout_act): each wave steps and acts
         # for its replicas round after round (MS_ENV_ROLLOUT=0: one launch per round, for A/B measurements)
@@ -310,7 +315,7 @@ class Trainer:
         # (MS_ENV_ROLLOUT_FREE=0: an act launch and an env launch per round, for A/B measurements)
         self.fused_rollout_free = (self.compact and self.free and arch == "local" and self.price_table is not None and
                                    self.off_frag is not None and not self.price_unit_major and self.T > 1 and
-                                   self.metric_bufs is None and os.environ.get("MS_ENV_ROLLOUT_FREE", "1") != "0" and
+                                   fused_metrics_ok and os.environ.get("MS_ENV_ROLLOUT_FREE", "1") != "0" and
                                    all(env.rollout_free_supported() for env, _, _ in self.env.parts))
         # ... and its acceptor items of cores their agent does not own (sampled from the common row's table; the env
         # reads only the owner's acceptor action) are left to a second kernel (ms_env_rollout_fill_common) after the
@@ -509,6 +514,8 @@ class Trainer:
         rew = dict(offer=sl(self.off.rewards[0]).view(E, N, L), acceptor=sl(self.acc.rewards[0]).view(E, N, C),
                    agent=sl(self.agent_reward), auctioneer=sl(self.auct_reward))
         ev = dict(launch_span=self.spans[0, k]) if self.span_every else None
+        if self.metric_bufs is not None:  # every round adds into the slot of its own episode (not strided)
+            ev = dict(ev or {}, metrics=self.metric_bufs[k])
         b = lambda x: x.stride(0) * x.element_size()  # bytes between ring slots t and t + 1
         strides = abi.MsRoundStrides(b(self.acc.actions), b(self.off.actions), b(self.acc_rows), b(self.acc_owner),
                                      b(self.off_obs), b(self.off.rewards), b(self.acc.rewards), 0, 0,
@@ -552,6 +559,8 @@ class Trainer:
                    agent=sl(self.agent_reward), auctioneer=sl(self.auct_reward),
                    price=sl(self.price.rewards[0]).view(E, N, L))
         ev = dict(launch_span=self.spans[0, k]) if self.span_every else None
+        if self.metric_bufs is not None:
+            ev = dict(ev or {}, metrics=self.metric_bufs[k])
         b = lambda x: x.stride(0) * x.element_size()  # bytes between ring slots t and t + 1
         strides = abi.MsRoundStridesFree(b(self.acc.actions), b(self.off.actions), b(self.acc_rows), b(self.acc_owner),
                                          b(self.off_obs), b(self.off.rewards), b(self.price.rewards),

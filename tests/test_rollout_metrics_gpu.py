@@ -1,0 +1,315 @@
+"""Episode metrics inside the one-launch rollouts (ABI 21): ms_env_step_act, ms_env_rollout_act (cfg2) and
+ms_env_rollout_act_free (cfg3) accumulate ms_env_metrics themselves, so Trainer(metrics=True) keeps the fused
+paths instead of falling back to an act launch and an env launch per round.
+
+The accumulators must equal those of ms_env_step bit for bit, the two doubles included: quality_sum receives one
+inexact term per round (a price over a remaining time of 3 or 6), so inside one launch the order of its adds is
+part of the contract (env_kernels.hip: the group leader's ordered read-modify-write). Every test compares raw
+bytes, with episode boundaries inside the launch (episode_length 7 against 20 or 21 rounds per rollout, 3 + 1
+slots that wrap across the two iterations), and asserts that the accumulators it compared are not empty."""
+import ctypes as ct
+import importlib
+
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+EP_LEN = 7
+
+
+def _rings(t):
+    out = {"acc_rows": t.acc_rows, "acc_owner": t.acc_owner, "off_obs": t.off_obs, "env_price": t.env_price,
+           "agent_reward": t.agent_reward, "auct_reward": t.auct_reward}
+    if t.price_obs is not None:
+        out["price_obs"] = t.price_obs
+    for u in t.units():
+        for k in ("actions", "logprobs", "rewards"):
+            out["%s.%s" % (u.name, k)] = getattr(u, k)
+    return out
+
+
+def _metric_bytes(t):
+    """The trainer's accumulators [slots][E][METRICS_BYTES] (uint8), its replica parts side by side."""
+    return torch.cat(list(t.metric_bufs), dim=1)
+
+
+def _assert_not_vacuous(ms, t, raw):
+    """The accumulators hold what the comparison is about: qualities (two rounds of one episode for some replica,
+    so the order of the double adds matters), prices, dwell times, and every round of every replica once."""
+    mx = importlib.import_module("marl-scheduling_amd.metrics")
+    m = mx.view(raw.cpu().numpy())  # [slots][E]
+    figures = dict(quality_rounds=int(m["quality_rounds"].sum()), price_count=int(m["price_count"].sum()),
+                   dwell_count=int(m["dwell_count"].sum()), max_quality_rounds=int(m["quality_rounds"].max()),
+                   rounds=int(m["rounds"].sum()), inexact=int((m["quality_sum"] * 8 % 1 != 0).sum()))
+    print("metrics figures", t.E, t.T, figures)
+    assert figures["quality_rounds"] > 0 and figures["price_count"] > 0 and figures["dwell_count"] > 0, figures
+    assert figures["max_quality_rounds"] >= 2, figures
+    # the rounds not harvested yet (iteration 0: E * T)
+    assert figures["rounds"] == t.E * (t.rounds_done - len(t.episode_log) * t.ep_len), figures
+
+
+def _logs_equal(a, b):
+    """episode_log entries (a list of per-replica dicts per episode) equal with ==, no tolerance."""
+    assert len(a) == len(b)
+    for ea, eb in zip(a, b):
+        assert len(ea) == len(eb)
+        for ra, rb in zip(ea, eb):
+            assert ra.keys() == rb.keys()
+            for k in ra:
+                if isinstance(ra[k], np.ndarray):
+                    assert (ra[k] == rb[k]).all(), k
+                else:
+                    assert ra[k] == rb[k], (k, ra[k], rb[k])
+
+
+def _state(t):
+    parts = [env.export_state() for env, _, _ in t.env.parts]
+    return {k: np.concatenate([p[k] for p in parts]) for k in parts[0]}
+
+
+def _compare(ms, trs, iters=2):
+    """trs[0] against every other trainer: after every rollout the raw accumulators (before anything harvests)
+    and every ring, after the update the losses and the harvested episodes; at the end weights and env state."""
+    ppo = importlib.import_module("marl-scheduling_amd.ppo")
+    for it in range(iters):
+        for t in trs:
+            t.rollout()
+        torch.cuda.synchronize()
+        raw = [_metric_bytes(t) for t in trs]
+        _assert_not_vacuous(ms, trs[0], raw[0])
+        rings = [_rings(t) for t in trs]
+        for i in range(1, len(trs)):
+            assert torch.equal(raw[0], raw[i]), (it, i, int((raw[0] != raw[i]).sum()))
+            for k in rings[0]:
+                same = rings[0][k] == rings[i][k]
+                assert bool(same.all()), (it, i, k, int((~same).sum()), same.numel())
+        losses = [t.update() for t in trs]
+        for t in trs:
+            t._harvest_episodes()
+        for i in range(1, len(trs)):
+            for k in losses[0]:
+                assert torch.equal(losses[0][k], losses[i][k]), (it, i, k)
+            assert len(trs[0].episode_log) == trs[0].rounds_done // EP_LEN > 0
+            _logs_equal(trs[0].episode_log, trs[i].episode_log)
+    st = [_state(t) for t in trs]
+    for i in range(1, len(trs)):
+        for u0, u1 in zip(trs[0].units(), trs[i].units()):
+            for k in ppo.ACTOR_KEYS + ppo.CRITIC_KEYS:
+                assert torch.equal(getattr(u0.group.policy, k), getattr(u1.group.policy, k)), (i, u0.name, k)
+        for k in st[0]:
+            assert (st[0][k] == st[i][k]).all(), (i, k)
+    assert all(t.flags() == 0 for t in trs)
+
+
+def _fused_and_plain(monkeypatch, mk, mk_plain=None):
+    fused = mk()
+    monkeypatch.setenv("MS_ROLLOUT_METRICS", "0")
+    plain = (mk_plain or mk)()
+    monkeypatch.delenv("MS_ROLLOUT_METRICS")
+    assert fused.metric_bufs is not None and plain.metric_bufs is not None
+    return fused, plain
+
+
+@pytest.mark.parametrize("E,T", [(64, 20), (33, 20)])
+def test_cfg3_one_launch_metrics_equal_two_launches(ms, monkeypatch, E, T):
+    """cfg3, FixShape<8,8,3,1>: E 64 is two full workgroups, E 33 leaves a last workgroup of one replica whose
+    padding groups must add nothing. The one-launch rollout with metrics against the launch-per-round trainer."""
+    tr_mod = importlib.import_module("marl-scheduling_amd.trainer")
+    mk = lambda: tr_mod.Trainer.from_named("cfg3", n_envs=E, update_step=T, seed=11, device="cuda:0", metrics=True,
+                                           episode_length=EP_LEN)
+    fused, plain = _fused_and_plain(monkeypatch, mk)
+    assert fused.fused_rollout_free and not plain.fused_rollout_free
+    assert fused.metric_slots == 4
+    _compare(ms, [fused, plain])
+
+
+def test_generic_shape_one_launch_metrics_equal_two_launches(ms, monkeypatch):
+    """6 x 6 x 3 with free prices runs the DynShape kernel (6 waves per workgroup, 24 replicas: E 40 leaves a
+    partial last workgroup); 21 rounds per rollout are exactly three episodes."""
+    abi = importlib.import_module("marl-scheduling_amd.abi")
+    tr_mod = importlib.import_module("marl-scheduling_amd.trainer")
+    cfg = abi.make_config(6, 6, 3, free_prices=True, commercial=True, **abi.EXP4_JOBS)
+    hp = tr_mod.Hyper(update_step=21, raw_k_epochs=2)
+    mk = lambda: tr_mod.Trainer(cfg, 40, arch="local", hyper=hp, seed=4, device="cuda:0", metrics=True,
+                                episode_length=EP_LEN)
+    fused, plain = _fused_and_plain(monkeypatch, mk)
+    assert fused.fused_rollout_free and not plain.fused_rollout_free
+    _compare(ms, [fused, plain])
+
+
+def test_cfg3_one_launch_metrics_of_parts(ms, monkeypatch):
+    """Two rollout streams (two parts of 32 replicas, each its own env, launch and accumulators) against the
+    single launch-per-round trainer."""
+    tr_mod = importlib.import_module("marl-scheduling_amd.trainer")
+    mk = lambda streams: tr_mod.Trainer.from_named("cfg3", n_envs=64, update_step=20, seed=7, device="cuda:0",
+                                                   metrics=True, episode_length=EP_LEN, rollout_streams=streams)
+    fused, plain = _fused_and_plain(monkeypatch, lambda: mk(2), lambda: mk(1))
+    assert fused.fused_rollout_free and not plain.fused_rollout_free and len(fused.metric_bufs) == 2
+    _compare(ms, [fused, plain])
+
+
+def test_cfg3_metrics_with_deferred_common_fill(ms, monkeypatch):
+    """MS_DEFER_COMMON=1 (the common acceptor items sampled inside the update, no regenerating gradient) with
+    metrics, through iteration() as a training run calls it (graph replay, harvest inside): episode logs,
+    the accumulators of the unfinished episode, rings and losses equal the launch-per-round trainer's."""
+    tr_mod = importlib.import_module("marl-scheduling_amd.trainer")
+    mk = lambda: tr_mod.Trainer.from_named("cfg3", n_envs=64, update_step=20, seed=3, device="cuda:0", metrics=True,
+                                           episode_length=EP_LEN)
+    monkeypatch.setenv("MS_DEFER_COMMON", "1")
+    fused = mk()
+    monkeypatch.delenv("MS_DEFER_COMMON")
+    monkeypatch.setenv("MS_ROLLOUT_METRICS", "0")
+    plain = mk()
+    monkeypatch.delenv("MS_ROLLOUT_METRICS")
+    assert fused.fused_rollout_free and fused.defer_common and not fused.acc_regen and not plain.fused_rollout_free
+    for it in range(3):
+        l0, l1 = fused.iteration(), plain.iteration()
+        torch.cuda.synchronize()
+        for k in l0:
+            assert torch.equal(l0[k], l1[k]), (it, k)
+        r0, r1 = _rings(fused), _rings(plain)
+        for k in r0:
+            assert torch.equal(r0[k], r1[k]), (it, k)
+        assert torch.equal(_metric_bytes(fused), _metric_bytes(plain)), it
+        assert len(fused.episode_log) == (it + 1) * 20 // EP_LEN
+        _logs_equal(fused.episode_log, plain.episode_log)
+    assert any(r["acceptionQuality"] is not None for ep in fused.episode_log for r in ep)
+    assert fused.flags() == 0 and plain.flags() == 0
+
+
+@pytest.mark.parametrize("E", [96, 1001, 4096])
+def test_cfg2_one_launch_metrics_equal_per_round_launches(ms, monkeypatch, E):
+    """cfg2 (fixed prices, one net per role): the whole rollout in one launch (ms_env_rollout_act), one fused
+    launch per round (ms_env_step_act) and the act + env launches per round (ms_env_step), all with metrics.
+    E 96 and 1001 run the 16-lane generic kernel (four replicas per wave; 1001: a last wave of one replica),
+    E 4096 32 lanes per replica with FixShape<4,4,3,1>."""
+    tr_mod = importlib.import_module("marl-scheduling_amd.trainer")
+    mk = lambda: tr_mod.Trainer.from_named("cfg2", n_envs=E, update_step=20, seed=5, device="cuda:0", metrics=True,
+                                           episode_length=EP_LEN)
+    whole = mk()
+    monkeypatch.setenv("MS_ENV_ROLLOUT", "0")
+    per_round = mk()
+    monkeypatch.delenv("MS_ENV_ROLLOUT")
+    monkeypatch.setenv("MS_ROLLOUT_METRICS", "0")
+    plain = mk()
+    monkeypatch.delenv("MS_ROLLOUT_METRICS")
+    assert whole.fused_rollout and whole.fused_step
+    assert per_round.fused_step and not per_round.fused_rollout
+    assert not plain.fused_step and not plain.fused_rollout
+    _compare(ms, [whole, per_round, plain])
+
+
+def test_cfg3_fused_metrics_equal_env_step_replay(ms):
+    """Independent of the trainer's launch-per-round path: the actions of a fused cfg3 rollout (E 33, T 20),
+    replayed round by round through a fresh BatchedEnv of the same seed with ms_env_step's metrics, give the
+    same accumulator bytes (ms_env_step's are pinned to the driver's restatement by tests/test_metrics_gpu.py)."""
+    tr_mod = importlib.import_module("marl-scheduling_amd.trainer")
+    E, T = 33, 20
+    t = tr_mod.Trainer.from_named("cfg3", n_envs=E, update_step=T, seed=11, device="cuda:0", metrics=True,
+                                  episode_length=EP_LEN)
+    assert t.fused_rollout_free
+    t.rollout()
+    torch.cuda.synchronize()
+    got = _metric_bytes(t)
+    _assert_not_vacuous(ms, t, got)
+    env = ms.BatchedEnv(t.cfg, E, seed=tr_mod.env_seed(t.seed, 0, E), device="cuda:0")
+    buf = env.metrics_buffer(t.metric_slots)
+    N, C, L = t.N, t.C, t.L
+    acc, off, price = t.acc.actions, t.off.actions, t.price.actions  # (acc.actions completes the rings)
+    for r in range(T):
+        env_price = torch.where(off[r] == 0, torch.full_like(price[r], -5), price[r])
+        env.step(acc[r].view(E, N, C).contiguous(), off[r].view(E, N, L).contiguous(),
+                 env_price.view(E, N, L).contiguous(), events=dict(metrics=buf))
+    torch.cuda.synchronize()
+    assert env.flags() == 0 and t.flags() == 0
+    assert torch.equal(got, buf), int((got != buf).sum())
+    st0, st1 = t.env.parts[0][0].export_state(), env.export_state()
+    for k in st0:
+        assert (st0[k] == st1[k]).all(), k
+
+
+def _round_sum(ms, buf):
+    mx = importlib.import_module("marl-scheduling_amd.metrics")
+    return int(mx.view(buf.cpu().numpy())["rounds"].sum())
+
+
+def test_rollout_act_free_takes_metrics(ms):
+    """ms_env_rollout_act_free with ev->metrics runs and advances the env by n_rounds; accepted / terminated
+    records stay refused, and so does a metrics array of no slots (MS_EINVAL, the env left where it was)."""
+    lib_mod = importlib.import_module("marl-scheduling_amd._lib")
+    abi = importlib.import_module("marl-scheduling_amd.abi")
+    tr_mod = importlib.import_module("marl-scheduling_amd.trainer")
+    t = tr_mod.Trainer.from_named("cfg3", n_envs=64, update_step=8, seed=2, device="cuda:0")
+    assert t.fused_rollout_free
+    t._prepare_acting()
+    t._act_part(0, 0)
+    env, e0, e1 = t.env.parts[0]
+    E, N, C, L = e1 - e0, t.N, t.C, t.L
+    obs = dict(t._acc_out(1, e0, e1), offer=t.off_obs[1])
+    rew = dict(offer=t.off.rewards[0].view(E, N, L), acceptor=t.acc.rewards[0].view(E, N, C), agent=t.agent_reward,
+               auctioneer=t.auct_reward, price=t.price.rewards[0].view(E, N, L))
+    b = lambda x: x.stride(0) * x.element_size()
+    strides = abi.MsRoundStridesFree(b(t.acc.actions), b(t.off.actions), b(t.acc_rows), b(t.acc_owner), b(t.off_obs),
+                                     b(t.off.rewards), b(t.price.rewards), b(t.acc.rewards), 0, 0, b(t.off.actions),
+                                     b(t.off.logprobs), b(t.price_obs), b(t.price.actions), b(t.price.logprobs),
+                                     b(t.acc.actions), b(t.acc.logprobs), 8)
+    nxt, out = t._fused_next_free(1, 0)
+    if t.acc_own is not None:
+        strides.next_own_action, strides.next_own_logprob = b(t.acc_own[0]), b(t.acc_own[1])
+    acc0, off0 = t.acc.actions[0].view(E, N, C), t.off.actions[0].view(E, N, L)
+    buf = env.metrics_buffer(2)
+    r0 = lib_mod.lib.ms_env_round(env._h)
+    with pytest.raises(lib_mod.MarlSchedError, match="event records"):
+        env.rollout_act_free(acc0, off0, obs, rew, nxt, out, strides, 3,
+                             events=dict(metrics=buf, accepted=torch.zeros((E, C, 16), dtype=torch.uint8,
+                                                                           device="cuda:0")))
+    # (a metrics array with metrics_slots 0: the struct by hand, an empty tensor has no pointer to give)
+    a, o, r, _ = env._step_structs(acc0, off0, out["env_price"], None, obs, rew, None)
+    ev = abi.MsEventOut(None, None, None, lib_mod.ptr(buf), 0)
+    rc = lib_mod.lib.ms_env_rollout_act_free(env._h, ct.byref(a), ct.byref(o), ct.byref(r), ct.byref(ev),
+                                             ct.byref(nxt), ct.byref(strides), 3, 0, lib_mod.stream_ptr())
+    assert rc == abi.EINVAL and b"metrics_slots" in lib_mod.lib.ms_last_error()
+    assert lib_mod.lib.ms_env_round(env._h) == r0
+    env.rollout_act_free(acc0, off0, obs, rew, nxt, out, strides, 3, events=dict(metrics=buf))
+    torch.cuda.synchronize()
+    assert lib_mod.lib.ms_env_round(env._h) == r0 + 3
+    assert _round_sum(ms, buf) == 3 * E and env.flags() == 0
+
+
+def test_rollout_act_takes_metrics(ms):
+    """The same for ms_env_rollout_act (cfg2)."""
+    lib_mod = importlib.import_module("marl-scheduling_amd._lib")
+    abi = importlib.import_module("marl-scheduling_amd.abi")
+    tr_mod = importlib.import_module("marl-scheduling_amd.trainer")
+    t = tr_mod.Trainer.from_named("cfg2", n_envs=96, update_step=8, seed=2, device="cuda:0")
+    assert t.fused_rollout
+    t._prepare_acting()
+    t._act_part(0, 0)
+    env, e0, e1 = t.env.parts[0]
+    E, N, C, L = e1 - e0, t.N, t.C, t.L
+    obs = dict(t._acc_out(1, e0, e1), offer=t.off_obs[1])
+    rew = dict(offer=t.off.rewards[0].view(E, N, L), acceptor=t.acc.rewards[0].view(E, N, C), agent=t.agent_reward,
+               auctioneer=t.auct_reward)
+    b = lambda x: x.stride(0) * x.element_size()
+    strides = abi.MsRoundStrides(b(t.acc.actions), b(t.off.actions), b(t.acc_rows), b(t.acc_owner), b(t.off_obs),
+                                 b(t.off.rewards), b(t.acc.rewards), 0, 0, b(t.off.actions), b(t.off.logprobs),
+                                 b(t.acc.actions), b(t.acc.logprobs), 8)
+    nxt = t._fused_next(1, 0)
+    acc0, off0 = t.acc.actions[0].view(E, N, C), t.off.actions[0].view(E, N, L)
+    buf = env.metrics_buffer(2)
+    r0 = lib_mod.lib.ms_env_round(env._h)
+    with pytest.raises(lib_mod.MarlSchedError, match="event records"):
+        env.rollout_act(acc0, off0, obs, rew, nxt, strides, 3,
+                        events=dict(metrics=buf, accepted=torch.zeros((E, C, 16), dtype=torch.uint8, device="cuda:0")))
+    a, o, r, _ = env._step_structs(acc0, off0, None, None, obs, rew, None)
+    ev = abi.MsEventOut(None, None, None, lib_mod.ptr(buf), 0)
+    rc = lib_mod.lib.ms_env_rollout_act(env._h, ct.byref(a), ct.byref(o), ct.byref(r), ct.byref(ev), ct.byref(nxt),
+                                        ct.byref(strides), 3, 0, lib_mod.stream_ptr())
+    assert rc == abi.EINVAL and b"metrics_slots" in lib_mod.lib.ms_last_error()
+    assert lib_mod.lib.ms_env_round(env._h) == r0
+    env.rollout_act(acc0, off0, obs, rew, nxt, strides, 3, events=dict(metrics=buf))
+    torch.cuda.synchronize()
+    assert lib_mod.lib.ms_env_round(env._h) == r0 + 3
+    assert _round_sum(ms, buf) == 3 * E and env.flags() == 0
