@@ -46,7 +46,11 @@ constexpr int kProbeSlots = 65536;
 __device__ unsigned long long g_phase_cycles[kProbeSlots][16];  // per block, summed on the host
 __device__ unsigned long long g_wave_span[kProbeSlots][2];      // last launch: s_memrealtime at entry / exit
 __device__ unsigned long long g_free_cycles[kProbeSlots][5];    // k_env_rollout_act_free: env, wait, offers, acceptors, wait
-#define MS_MARK(k)                                                     \
+// k_env_rollout_act_free, last launch, per workgroup: [0] bit 63 set, the CU rank in bit 32, the CU key below;
+// [1 + k] the s_memrealtime after the round's first barrier, rounds 0..63 and the last 16 (tools/free_stagger_probe.py)
+constexpr int kProbeWgs = 4096, kProbeRoundsHead = 64, kProbeRoundsTail = 16;
+__device__ unsigned long long g_free_rounds[kProbeWgs][1 + kProbeRoundsHead + kProbeRoundsTail];
+#define MS_MARK(k)                                                    \
     do {                                                               \
         const uint64_t t_now = __builtin_amdgcn_s_memtime();          \
         t_acc[k] += t_now - t_prev;                                    \
@@ -1979,13 +1983,27 @@ __device__ __forceinline__ uint32_t pick4u(const uint32_t (&v)[4], int k) {
 // another stream): the env reads only the owner's acceptor action (world.py:391-404), so their sampling is off the
 // round's chain. (Sampling them here as well, k_act_common's table search per item: 50.2 us per round against
 // 47.4, profiles/r7g.)
-template <class SH, int PART = 3>  // PART bit 0: the offer units, bit 1: the acceptors (the probe build times them apart)
+// The staggered launch's priority pair of a workgroup's acting (wave-uniform): < 0 no separation, 0 the lower pair
+// of levels (0, 1), 1 the upper (2, 3), 2 + rank with the slice's log2 from bit 2 up: the two workgroups of a CU
+// take the upper pair in turns, by slices of the 100 MHz clock both read (rank 0 in the even slices), so neither
+// is the older, favoured one for long.
+__device__ __forceinline__ bool stagger_upper_pair(int pair) {
+    if (pair < 2) return pair != 0;
+    const uint32_t slice = (uint32_t)(__builtin_amdgcn_s_memrealtime() >> ((pair >> 2) & 31));
+    return __builtin_amdgcn_readfirstlane((int)((slice ^ (uint32_t)pair) & 1u)) == 0;
+}
+// SEP (the staggered kernels): prio_upper, see pace
+template <class SH, int PART = 3, bool SEP = false>  // PART bit 0: the offer units, bit 1: the acceptors (the probe build times them apart)
 __device__ __forceinline__ void act_free(const Geom& g, int64_t E, const FusedActFree& fa, int64_t e0, int a, int lane,
-                                         uint8_t* lds, const FreeLds& fl, bool pace_on = false) {
+                                         uint8_t* lds, const FreeLds& fl, bool pace_on = false,
+                                         int prio_upper = 0) {
     const int j = lane & 15, g4 = lane >> 4;
     // pace_on: waves a and a ^ 4 share a SIMD, where issue goes to the older wave first, so one of them finishes
     // its acting well before the other and waits at the round's barrier. After each step (a tile pair, a 64-item
     // scan) a wave counts it in the LDS and raises its issue priority while it is behind its partner.
+    // prio_upper (SEP; wave-uniform: the staggered launch's priority separation): the toggle is between levels 2
+    // and 3 instead of 0 and 1. (Read through an opaque copy: as a loop invariant it had the compiler build every
+    // tile loop twice, 13.6k instructions for 11.9k and 200 more lane moves.)
     const int partner = a ^ 4;
     const bool pacing = pace_on && partner < g.N;
     auto pace = [&]() {
@@ -1994,7 +2012,19 @@ __device__ __forceinline__ void act_free(const Geom& g, int64_t E, const FusedAc
         const int mine = pg[a] + 1;
         pg[a] = mine;
         const int other = __builtin_amdgcn_readfirstlane(pg[partner]);
-        if (other > __builtin_amdgcn_readfirstlane(mine))
+        const bool behind = other > __builtin_amdgcn_readfirstlane(mine);
+        if constexpr (SEP) {
+            int upper = __builtin_amdgcn_readfirstlane(prio_upper);
+            asm volatile("" : "+s"(upper));
+            if (upper) {
+                if (behind)
+                    __builtin_amdgcn_s_setprio(3);
+                else
+                    __builtin_amdgcn_s_setprio(2);
+                return;
+            }
+        }
+        if (behind)
             __builtin_amdgcn_s_setprio(1);
         else
             __builtin_amdgcn_s_setprio(0);
@@ -2549,7 +2579,23 @@ struct RolloutFreeArgs {
     int n_rounds, act_last;
     int prio;  // bit 0: the workgroup's waves 4.. at raised issue priority while acting, bit 1: during the env round,
                // bit 2: the acting's waves paced against their SIMD partners (act_free pace_on)
+    int stagger;        // (STAG kernels) bit 0: the CU's rank-1 workgroup sleeps stagger_delay cycles before round 0,
+                        // bit 1: the env rounds at priority 3, the acting at 2..3 (rank 0) or 0..1 (rank 1),
+                        // bit 2: as bit 1, the two ranks at 2..3 in turns, 2^stagger_slice clock ticks each
+    int stagger_delay;  // s_memtime cycles
+    int stagger_slice;  // log2 of s_memrealtime ticks (100 MHz)
 };
+// The CU a wave runs on, 12 bits: HW_REG_XCC_ID's XCC above HW_REG_HW_ID's SE, SH and CU fields (bits 15..8).
+constexpr int kCuKeys = 1 << 12;
+__device__ __forceinline__ uint32_t cu_key() {
+    const uint32_t cu = __builtin_amdgcn_s_getreg(4 | (8 << 6) | (7 << 11));  // HW_ID, offset 8, 8 bits
+    const uint32_t xcc = __builtin_amdgcn_s_getreg(20 | (3 << 11));          // XCC_ID, offset 0, 4 bits
+    return (xcc << 8 | cu) & (kCuKeys - 1);
+}
+// Arrivals per CU of the staggered launches' workgroups, never reset: a CU that holds two workgroups of a launch
+// gets two arrivals per launch, so the parity of a ticket tells them apart in every launch. Only the timing of a
+// workgroup depends on its ticket; nothing waits for another workgroup's.
+__device__ uint32_t g_cu_ticket[kCuKeys];
 // The locally shared free-price rollout in one launch: workgroup b holds replicas kFreeEPW * N * b .. in its LDS,
 // and wave w steps kFreeEPW of them (k_env_step's round, 16 lanes per replica) and then acts for agent w of all
 // of them (act_free), round after round, with a workgroup barrier between the phases: every agent's nets
@@ -2557,7 +2603,12 @@ struct RolloutFreeArgs {
 // HBM. Round t's arrays are the given ones advanced by t strides. The round re-reads its arguments through
 // the opaque kernel-argument pointer (k_env_rollout_act). Two workgroups per CU: 4 waves per SIMD (<= 128 VGPRs).
 // MET: every round adds its episode metrics (env_round; the padding groups of a partial last workgroup add nothing).
-template <class SH, bool MET = false>
+// STAG (MS_FREE_STAGGER != 0): the two workgroups of a CU told apart. Left alone they drift to a random phase
+// within a few rounds, and the older one, which wins issue, runs its rounds a quarter faster and leaves the other
+// to finish alone (profiles/r10a). Each workgroup takes a rank from its CU's ticket (g_cu_ticket);
+// RolloutFreeArgs::stagger says what the rank does: the default gives the env phase the highest priority and the
+// two ranks the higher acting priority in turns. A workgroup's results do not depend on its rank.
+template <class SH, bool MET = false, bool STAG = false>
 __global__ void __launch_bounds__(512, 4) k_env_rollout_act_free(RolloutFreeArgs A0) {
     extern __shared__ __align__(16) uint8_t smem_free[];
     Geom g;
@@ -2589,7 +2640,27 @@ __global__ void __launch_bounds__(512, 4) k_env_rollout_act_free(RolloutFreeArgs
         for (int k = (int)threadIdx.x; k < (fl.total - fl.accx) / 4; k += (int)blockDim.x) ax[k] = 0u;  // (+ pace)
     }
     __syncthreads();
+    [[maybe_unused]] int prio_pair = -1;
+    [[maybe_unused]] int rank = 0;
+    if constexpr (STAG) {
+        // the rank goes through wave 0's pace word, which is free until the first acting: written back to zero
+        // after every wave has read it, and the round's first barrier comes before any wave paces
+        volatile int* pg = reinterpret_cast<volatile int*>(smem_free + fl.pace);
+        if (threadIdx.x == 0) pg[0] = (int)(atomicAdd(&g_cu_ticket[cu_key()], 1u) & 1u);
+        __syncthreads();
+        rank = __builtin_amdgcn_readfirstlane(pg[0]);
+        __syncthreads();
+        if (threadIdx.x == 0) pg[0] = 0;
+        if (rank != 0 && (A0.stagger & 1)) {  // ended by the clock alone
+            const uint64_t t0 = __builtin_amdgcn_s_memtime(), d = (uint64_t)(uint32_t)A0.stagger_delay;
+            while (__builtin_amdgcn_s_memtime() - t0 < d) __builtin_amdgcn_s_sleep(8);
+        }
+        if (A0.stagger & 6)
+            prio_pair = (A0.stagger & 4) ? (A0.stagger_slice & 31) << 2 | 2 | rank : (rank == 0 ? 1 : 0);
+    }
 #ifdef MS_PHASE_TIMING
+    if (threadIdx.x == 0 && blockIdx.x < kProbeWgs)
+        g_free_rounds[blockIdx.x][0] = 1ull << 63 | (unsigned long long)rank << 32 | cu_key();
     // probe build: per wave, the shader cycles of the env rounds, the wait at the barrier after them, the acting,
     // and the wait at the barrier after it (tools/env_phase_probe.py --free)
     uint64_t f_prev = __builtin_amdgcn_s_memtime(), f_acc[5] = {0, 0, 0, 0, 0};
@@ -2629,6 +2700,12 @@ __global__ void __launch_bounds__(512, 4) k_env_rollout_act_free(RolloutFreeArgs
         //  priority, then age)
         const bool up = wave >= 4 && (A.prio & 2);
         if (up) __builtin_amdgcn_s_setprio(1);
+        [[maybe_unused]] int prio_upper = 0;
+        if constexpr (STAG) {
+            prio_pair = __builtin_amdgcn_readfirstlane(prio_pair);
+            asm volatile("" : "+s"(prio_pair));  // (not a loop invariant to the compiler, as in act_free's pace)
+            if (prio_pair >= 0) __builtin_amdgcn_s_setprio(3);
+        }
         // rounds after the first (by-core mode): the owners' acceptor actions are where this launch's acting left
         // them in the LDS (the rings' acceptor rows are written after the launch, by the fill)
         const int8_t* acc_lds = t > 0 && A.fa.own_action
@@ -2637,10 +2714,26 @@ __global__ void __launch_bounds__(512, 4) k_env_rollout_act_free(RolloutFreeArgs
         env_round<kWave / kFreeEPW, false, true, SH, MET, MET>(A.P, A.E, A.recs, A.mt, A.liab, io, wslot, lane,
                                                                smem_free + wave * free_slot(g), acc_lds);
         if (up) __builtin_amdgcn_s_setprio(0);
+        if constexpr (STAG) {
+            if (prio_pair >= 0) {  // this round's acting: the pair by now's clock slice
+                prio_upper = stagger_upper_pair(prio_pair) ? 1 : 0;
+                if (prio_upper)
+                    __builtin_amdgcn_s_setprio(2);
+                else
+                    __builtin_amdgcn_s_setprio(0);
+            }
+        }
         FREE_MARK(0);
         if (t + 1 < n_rounds || A.act_last) {
             __syncthreads();  // every replica's observation sources are in the LDS
             FREE_MARK(1);
+#ifdef MS_PHASE_TIMING
+            if (threadIdx.x == 0 && blockIdx.x < kProbeWgs) {
+                const int tail = t - (n_rounds - kProbeRoundsTail);
+                const int k = t < kProbeRoundsHead ? t : (tail >= 0 ? kProbeRoundsHead + tail : -1);
+                if (k >= 0) g_free_rounds[blockIdx.x][1 + k] = __builtin_amdgcn_s_memrealtime();
+            }
+#endif
             FusedActFree fa = A.fa;
             fa.core_action = advance(fa.core_action, t * st.core_action);
             fa.core_logprob = advance(fa.core_logprob, t * st.core_logprob);
@@ -2657,11 +2750,11 @@ __global__ void __launch_bounds__(512, 4) k_env_rollout_act_free(RolloutFreeArgs
             if (up_act) __builtin_amdgcn_s_setprio(1);
             const bool pace_on = (A.prio & 4) != 0;
 #ifdef MS_PHASE_TIMING
-            act_free<SH, 1>(g, A.E, fa, (int64_t)blockIdx.x * kFreeEPW * g.N, wave, lane, smem_free, fl, pace_on);
+            act_free<SH, 1, STAG>(g, A.E, fa, (int64_t)blockIdx.x * kFreeEPW * g.N, wave, lane, smem_free, fl, pace_on, prio_upper);
             FREE_MARK(2);
-            act_free<SH, 2>(g, A.E, fa, (int64_t)blockIdx.x * kFreeEPW * g.N, wave, lane, smem_free, fl, pace_on);
+            act_free<SH, 2, STAG>(g, A.E, fa, (int64_t)blockIdx.x * kFreeEPW * g.N, wave, lane, smem_free, fl, pace_on, prio_upper);
 #else
-            act_free<SH>(g, A.E, fa, (int64_t)blockIdx.x * kFreeEPW * g.N, wave, lane, smem_free, fl, pace_on);
+            act_free<SH, 3, STAG>(g, A.E, fa, (int64_t)blockIdx.x * kFreeEPW * g.N, wave, lane, smem_free, fl, pace_on, prio_upper);
 #endif
             if (up_act || pace_on) __builtin_amdgcn_s_setprio(0);
             FREE_MARK(3);
@@ -2734,6 +2827,16 @@ __global__ void __launch_bounds__(64) k_env_randbelow(Params P, uint8_t* recs, u
 
 }  // namespace ms
 
+// Diagnostic, not part of the ABI (tests, tools): the tickets the staggered rollout launches have taken so far on
+// the current device, one per workgroup (synchronises the device).
+extern "C" long long ms_free_stagger_tickets(void) {
+    static uint32_t host[ms::kCuKeys];
+    if (hipMemcpyFromSymbol(host, HIP_SYMBOL(ms::g_cu_ticket), sizeof(host)) != hipSuccess) return -1;
+    long long n = 0;
+    for (int k = 0; k < ms::kCuKeys; k++) n += host[k];
+    return n;
+}
+
 #ifdef MS_PHASE_TIMING
 // profiling build only: read (and optionally clear) the per-phase cycle counters
 extern "C" int ms_probe_phase_cycles(unsigned long long* out, int clear) {
@@ -2776,6 +2879,15 @@ extern "C" int ms_probe_wave_spans(unsigned long long* out, int n_blocks) {
     if (n_blocks > ms::kProbeSlots) return -1;
     if (hipMemcpyFromSymbol(host, HIP_SYMBOL(ms::g_wave_span), sizeof(host)) != hipSuccess) return -1;
     memcpy(out, host, sizeof(unsigned long long) * 2 * n_blocks);
+    return 0;
+}
+// k_env_rollout_act_free's last launch: out[81 * n_wgs], per workgroup its CU word and round stamps (g_free_rounds)
+extern "C" int ms_probe_free_rounds(unsigned long long* out, int n_wgs) {
+    constexpr int W = 1 + ms::kProbeRoundsHead + ms::kProbeRoundsTail;
+    static unsigned long long host[ms::kProbeWgs][W];
+    if (n_wgs > ms::kProbeWgs) return -1;
+    if (hipMemcpyFromSymbol(host, HIP_SYMBOL(ms::g_free_rounds), sizeof(host)) != hipSuccess) return -1;
+    memcpy(out, host, sizeof(unsigned long long) * W * n_wgs);
     return 0;
 }
 #endif
@@ -2932,6 +3044,11 @@ hipError_t launch_env_rollout_act(const Params& P, int64_t E, uint8_t* recs, uin
 bool env_rollout_free_supported(const Params& P) {
     return P.free_prices && free_rollout_shape_ok(P) && free_rollout_lds_ok(P);
 }
+// MS_FREE_STAGGER's default (measured: 17.26 -> 16.48 ms per cfg3 iteration, slices of 2^14 .. 2^18 ticks alike,
+// profiles/r10a) and the start delay of its bit 0: half a round of the plain kernel in shader cycles, at most a
+// few rounds
+constexpr int kFreeStaggerDefault = 4, kFreeStaggerSlice = 16;
+constexpr long kFreeStaggerDelay = 49000, kFreeStaggerDelayMax = 1 << 20;
 template <class SH>
 static hipError_t launch_rollout_free_sh(const Params& P, int64_t E, uint8_t* recs, uint32_t* mt, Liab* liab,
                                          const StepIO& io, const FusedActFree& fa, const RoundStrideFree& st,
@@ -2944,8 +3061,20 @@ static hipError_t launch_rollout_free_sh(const Params& P, int64_t E, uint8_t* re
         // 47.07 -> 46.66 us against 1 over three A/B pairs, wait after acting 9.0k -> 4.5k cycles (profiles/r7)
         return v ? atoi(v) : 4;
     }();
-    const RolloutFreeArgs A{P, E, recs, mt, liab, io, fa, st, n_rounds, act_last, prio};
-    auto kern = io.metrics ? k_env_rollout_act_free<SH, true> : k_env_rollout_act_free<SH, false>;
+    // MS_FREE_STAGGER (read at every launch; a captured launch keeps what it was captured with): 0 the plain
+    // kernel, 1 the rank-1 workgroup of a CU starts MS_FREE_STAGGER_DELAY cycles late, 2 the two workgroups
+    // apart by issue priority, 3 both, 4 / 5 as 2 / 3 with the higher priority going to the two workgroups in
+    // turns (slices of 2^MS_FREE_STAGGER_SLICE ticks of the 100 MHz clock)
+    const char* sv = getenv("MS_FREE_STAGGER");
+    const int stagger = sv ? atoi(sv) & 7 : kFreeStaggerDefault;
+    const char* lv = getenv("MS_FREE_STAGGER_SLICE");
+    const int slice = lv ? atoi(lv) & 31 : kFreeStaggerSlice;
+    const char* dv = getenv("MS_FREE_STAGGER_DELAY");
+    long delay = dv ? atol(dv) : kFreeStaggerDelay;
+    delay = delay < 0 ? 0 : (delay > kFreeStaggerDelayMax ? kFreeStaggerDelayMax : delay);
+    const RolloutFreeArgs A{P, E, recs, mt, liab, io, fa, st, n_rounds, act_last, prio, stagger, (int)delay, slice};
+    auto kern = stagger ? (io.metrics ? k_env_rollout_act_free<SH, true, true> : k_env_rollout_act_free<SH, false, true>)
+                        : (io.metrics ? k_env_rollout_act_free<SH, true> : k_env_rollout_act_free<SH, false>);
     hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(64 * P.N), (size_t)free_lds(P).total, s, A);
     return hipGetLastError();
 }
