@@ -1983,14 +1983,15 @@ __device__ __forceinline__ uint32_t pick4u(const uint32_t (&v)[4], int k) {
 // another stream): the env reads only the owner's acceptor action (world.py:391-404), so their sampling is off the
 // round's chain. (Sampling them here as well, k_act_common's table search per item: 50.2 us per round against
 // 47.4, profiles/r7g.)
-// The staggered launch's priority pair of a workgroup's acting (wave-uniform): < 0 no separation, 0 the lower pair
-// of levels (0, 1), 1 the upper (2, 3), 2 + rank with the slice's log2 from bit 2 up: the two workgroups of a CU
-// take the upper pair in turns, by slices of the 100 MHz clock both read (rank 0 in the even slices), so neither
-// is the older, favoured one for long.
-__device__ __forceinline__ bool stagger_upper_pair(int pair) {
-    if (pair < 2) return pair != 0;
-    const uint32_t slice = (uint32_t)(__builtin_amdgcn_s_memrealtime() >> ((pair >> 2) & 31));
-    return __builtin_amdgcn_readfirstlane((int)((slice ^ (uint32_t)pair) & 1u)) == 0;
+// The staggered launch's acting priority (wave-uniform): the two workgroups of a CU take the upper pair of levels
+// (2, 3) in turns, the other the lower pair (0, 1), by slices of 2^kFreeStaggerSlice ticks of the 100 MHz clock
+// both read (rank 0 in the even slices), so neither is the older, favoured one for long. (Slices of 2^14 .. 2^18
+// ticks measured alike; a fixed pair per rank and a start delay for rank 1 were slower or no different and are
+// gone, profiles/r10a/ab_modes.json.)
+constexpr int kFreeStaggerSlice = 16;
+__device__ __forceinline__ bool stagger_upper_pair(int rank) {
+    const uint32_t slice = (uint32_t)(__builtin_amdgcn_s_memrealtime() >> kFreeStaggerSlice);
+    return __builtin_amdgcn_readfirstlane((int)((slice ^ (uint32_t)rank) & 1u)) == 0;
 }
 // SEP (the staggered kernels): prio_upper, see pace
 template <class SH, int PART = 3, bool SEP = false>  // PART bit 0: the offer units, bit 1: the acceptors (the probe build times them apart)
@@ -2419,7 +2420,7 @@ __global__ void __launch_bounds__(256) k_acc_common_fill(CommonFillArgs p) {
 // largest VALU cost: 32-bit multiplies at quarter rate). Same values bit for bit.
 constexpr int kFillRounds = 8;
 template <bool PAIR>
-__global__ void __launch_bounds__(256) k_acc_common_fill4(CommonFillArgs p, int n_acts, int merge) {  // merge: fill_merge()
+__global__ void __launch_bounds__(256) k_acc_common_fill4(CommonFillArgs p, int n_acts) {
     __shared__ __align__(16) float tabs[8 * kFreeTabDw];
     using FL = FragLayout<2, 2>;
     for (int k = threadIdx.x; k < p.N * kFreeTabDw; k += blockDim.x) {
@@ -2466,37 +2467,29 @@ __global__ void __launch_bounds__(256) k_acc_common_fill4(CommonFillArgs p, int 
         const size_t r = (size_t)e * U + u;
         int8_t* ad = advance(p.action, (int64_t)t * p.action_stride) + r;
         float* ld = advance(p.logprob, (int64_t)t * p.logprob_stride) + r;
-        if (owned == 0 || merge || p.own_action) {
-            uint32_t a4 = acts;
-            float4 l4 = make_float4(lps[0], lps[1], lps[2], lps[3]);
-            if (owned != 0) {  // merge the owned items the rollout wrote: whole quads, no partially written lines
-                // (by core [E][C]: cores c0..c0 + 3 of replica e; else the rings' own quad)
-                const size_t oc = (size_t)e * C + c0;
-                const uint32_t old_a = p.own_action
-                                           ? *reinterpret_cast<const uint32_t*>(advance(p.own_action, (int64_t)t * p.own_action_stride) + oc)
-                                           : *reinterpret_cast<const uint32_t*>(ad);
-                const float4 old_l = p.own_action
-                                         ? *reinterpret_cast<const float4*>(advance(p.own_logprob, (int64_t)t * p.own_logprob_stride) + oc)
-                                         : *reinterpret_cast<const float4*>(ld);
-                uint32_t m = 0;
+        uint32_t a4 = acts;
+        float4 l4 = make_float4(lps[0], lps[1], lps[2], lps[3]);
+        if (owned != 0) {  // merge the owned items the rollout wrote: whole quads, no partially written lines (the
+            // per-item stores left every line partial: 501 -> 425 us per 199-round fill, profiles/r7s)
+            // (by core [E][C]: cores c0..c0 + 3 of replica e; else the rings' own quad)
+            const size_t oc = (size_t)e * C + c0;
+            const uint32_t old_a = p.own_action
+                                       ? *reinterpret_cast<const uint32_t*>(advance(p.own_action, (int64_t)t * p.own_action_stride) + oc)
+                                       : *reinterpret_cast<const uint32_t*>(ad);
+            const float4 old_l = p.own_action
+                                     ? *reinterpret_cast<const float4*>(advance(p.own_logprob, (int64_t)t * p.own_logprob_stride) + oc)
+                                     : *reinterpret_cast<const float4*>(ld);
+            uint32_t m = 0;
 #pragma unroll
-                for (int k = 0; k < 4; k++) m |= ((owned >> k) & 1) ? 0xffu << (8 * k) : 0u;
-                a4 = (acts & ~m) | (old_a & m);
-                if (owned & 1) l4.x = old_l.x;
-                if (owned & 2) l4.y = old_l.y;
-                if (owned & 4) l4.z = old_l.z;
-                if (owned & 8) l4.w = old_l.w;
-            }
-            *reinterpret_cast<uint32_t*>(ad) = a4;
-            *reinterpret_cast<float4*>(ld) = l4;
-        } else {
-#pragma unroll
-            for (int k = 0; k < 4; k++)
-                if (!((owned >> k) & 1)) {
-                    ad[k] = (int8_t)(acts >> (8 * k));
-                    ld[k] = lps[k];
-                }
+            for (int k = 0; k < 4; k++) m |= ((owned >> k) & 1) ? 0xffu << (8 * k) : 0u;
+            a4 = (acts & ~m) | (old_a & m);
+            if (owned & 1) l4.x = old_l.x;
+            if (owned & 2) l4.y = old_l.y;
+            if (owned & 4) l4.z = old_l.z;
+            if (owned & 8) l4.w = old_l.w;
         }
+        *reinterpret_cast<uint32_t*>(ad) = a4;
+        *reinterpret_cast<float4*>(ld) = l4;
     };
 #pragma unroll
     for (int j = 0; j < kFillRounds; j++) {
@@ -2577,13 +2570,11 @@ struct RolloutFreeArgs {
     FusedActFree fa;
     RoundStrideFree st;
     int n_rounds, act_last;
-    int prio;  // bit 0: the workgroup's waves 4.. at raised issue priority while acting, bit 1: during the env round,
-               // bit 2: the acting's waves paced against their SIMD partners (act_free pace_on)
-    int stagger;        // (STAG kernels) bit 0: the CU's rank-1 workgroup sleeps stagger_delay cycles before round 0,
-                        // bit 1: the env rounds at priority 3, the acting at 2..3 (rank 0) or 0..1 (rank 1),
-                        // bit 2: as bit 1, the two ranks at 2..3 in turns, 2^stagger_slice clock ticks each
-    int stagger_delay;  // s_memtime cycles
-    int stagger_slice;  // log2 of s_memrealtime ticks (100 MHz)
+    // The launcher's constants kFreePrio and kFreeSeparate. They are arguments, and the branches they select stay
+    // in the kernel, because the kernel without them came out slower (profiles/r11_knobs).
+    int prio;      // bit 0: the workgroup's waves 4.. at raised issue priority while acting, bit 1: during the env
+                   // round, bit 2: the acting's waves paced against their SIMD partners (act_free pace_on)
+    int separate;  // (STAG kernels) != 0: the env rounds at priority 3, the acting by stagger_upper_pair
 };
 // The CU a wave runs on, 12 bits: HW_REG_XCC_ID's XCC above HW_REG_HW_ID's SE, SH and CU fields (bits 15..8).
 constexpr int kCuKeys = 1 << 12;
@@ -2605,9 +2596,9 @@ __device__ uint32_t g_cu_ticket[kCuKeys];
 // MET: every round adds its episode metrics (env_round; the padding groups of a partial last workgroup add nothing).
 // STAG (MS_FREE_STAGGER != 0): the two workgroups of a CU told apart. Left alone they drift to a random phase
 // within a few rounds, and the older one, which wins issue, runs its rounds a quarter faster and leaves the other
-// to finish alone (profiles/r10a). Each workgroup takes a rank from its CU's ticket (g_cu_ticket);
-// RolloutFreeArgs::stagger says what the rank does: the default gives the env phase the highest priority and the
-// two ranks the higher acting priority in turns. A workgroup's results do not depend on its rank.
+// to finish alone (profiles/r10a). Each workgroup takes a rank from its CU's ticket (g_cu_ticket): the env phase
+// runs at the highest priority and the two ranks take the higher acting priority in turns (stagger_upper_pair).
+// A workgroup's results do not depend on its rank.
 template <class SH, bool MET = false, bool STAG = false>
 __global__ void __launch_bounds__(512, 4) k_env_rollout_act_free(RolloutFreeArgs A0) {
     extern __shared__ __align__(16) uint8_t smem_free[];
@@ -2640,7 +2631,7 @@ __global__ void __launch_bounds__(512, 4) k_env_rollout_act_free(RolloutFreeArgs
         for (int k = (int)threadIdx.x; k < (fl.total - fl.accx) / 4; k += (int)blockDim.x) ax[k] = 0u;  // (+ pace)
     }
     __syncthreads();
-    [[maybe_unused]] int prio_pair = -1;
+    [[maybe_unused]] int prio_rank = -1;  // < 0: no separation
     [[maybe_unused]] int rank = 0;
     if constexpr (STAG) {
         // the rank goes through wave 0's pace word, which is free until the first acting: written back to zero
@@ -2651,12 +2642,7 @@ __global__ void __launch_bounds__(512, 4) k_env_rollout_act_free(RolloutFreeArgs
         rank = __builtin_amdgcn_readfirstlane(pg[0]);
         __syncthreads();
         if (threadIdx.x == 0) pg[0] = 0;
-        if (rank != 0 && (A0.stagger & 1)) {  // ended by the clock alone
-            const uint64_t t0 = __builtin_amdgcn_s_memtime(), d = (uint64_t)(uint32_t)A0.stagger_delay;
-            while (__builtin_amdgcn_s_memtime() - t0 < d) __builtin_amdgcn_s_sleep(8);
-        }
-        if (A0.stagger & 6)
-            prio_pair = (A0.stagger & 4) ? (A0.stagger_slice & 31) << 2 | 2 | rank : (rank == 0 ? 1 : 0);
+        if (A0.separate) prio_rank = rank;
     }
 #ifdef MS_PHASE_TIMING
     if (threadIdx.x == 0 && blockIdx.x < kProbeWgs)
@@ -2702,9 +2688,9 @@ __global__ void __launch_bounds__(512, 4) k_env_rollout_act_free(RolloutFreeArgs
         if (up) __builtin_amdgcn_s_setprio(1);
         [[maybe_unused]] int prio_upper = 0;
         if constexpr (STAG) {
-            prio_pair = __builtin_amdgcn_readfirstlane(prio_pair);
-            asm volatile("" : "+s"(prio_pair));  // (not a loop invariant to the compiler, as in act_free's pace)
-            if (prio_pair >= 0) __builtin_amdgcn_s_setprio(3);
+            prio_rank = __builtin_amdgcn_readfirstlane(prio_rank);
+            asm volatile("" : "+s"(prio_rank));  // (not a loop invariant to the compiler, as in act_free's pace)
+            if (prio_rank >= 0) __builtin_amdgcn_s_setprio(3);
         }
         // rounds after the first (by-core mode): the owners' acceptor actions are where this launch's acting left
         // them in the LDS (the rings' acceptor rows are written after the launch, by the fill)
@@ -2715,8 +2701,8 @@ __global__ void __launch_bounds__(512, 4) k_env_rollout_act_free(RolloutFreeArgs
                                                                smem_free + wave * free_slot(g), acc_lds);
         if (up) __builtin_amdgcn_s_setprio(0);
         if constexpr (STAG) {
-            if (prio_pair >= 0) {  // this round's acting: the pair by now's clock slice
-                prio_upper = stagger_upper_pair(prio_pair) ? 1 : 0;
+            if (prio_rank >= 0) {  // this round's acting: the pair by now's clock slice
+                prio_upper = stagger_upper_pair(prio_rank) ? 1 : 0;
                 if (prio_upper)
                     __builtin_amdgcn_s_setprio(2);
                 else
@@ -2912,20 +2898,17 @@ hipError_t launch_env_reset(const Params& P, int64_t E, const uint8_t* recs, int
 #ifndef MS_MIN_LPE
 #define MS_MIN_LPE 16
 #endif
-// A launch of >= 1024 replicas in fewer than MS_ENV_MIN_WAVES waves (env variable, default 2048: two per
-// SIMD) widens the lane groups up to that many waves, so the chip's SIMDs each hold two waves
+// A launch of >= 1024 replicas in fewer than kEnvMinWaves waves (two per SIMD) widens the lane groups up to
+// that many waves, so the chip's SIMDs each hold two waves
 // whose waits can hide each other: cfg2 (4096 replicas, 4 x 4) runs 32 lanes per env, 2048 waves,
 // instead of 16 lanes, 1024 waves (one per SIMD, every wait exposed).
+constexpr long long kEnvMinWaves = 2048;
 static int lanes_per_env(const Params& P, int64_t E) {
     int need = P.C > P.N ? P.C : P.N;
     int lpe = MS_MIN_LPE;
     while (lpe < need) lpe *= 2;
-    static const long long min_waves = [] {
-        const char* v = getenv("MS_ENV_MIN_WAVES");
-        return v ? atoll(v) : 2048LL;
-    }();
-    while (E >= 1024 && lpe < kWave && (E * lpe + kWave - 1) / kWave < min_waves &&
-           (E * 2 * lpe + kWave - 1) / kWave <= min_waves)
+    while (E >= 1024 && lpe < kWave && (E * lpe + kWave - 1) / kWave < kEnvMinWaves &&
+           (E * 2 * lpe + kWave - 1) / kWave <= kEnvMinWaves)
         lpe *= 2;
     return lpe;
 }
@@ -3044,65 +3027,25 @@ hipError_t launch_env_rollout_act(const Params& P, int64_t E, uint8_t* recs, uin
 bool env_rollout_free_supported(const Params& P) {
     return P.free_prices && free_rollout_shape_ok(P) && free_rollout_lds_ok(P);
 }
-// MS_FREE_STAGGER's default (measured: 17.26 -> 16.48 ms per cfg3 iteration, slices of 2^14 .. 2^18 ticks alike,
-// profiles/r10a) and the start delay of its bit 0: half a round of the plain kernel in shader cycles, at most a
-// few rounds
-constexpr int kFreeStaggerDefault = 4, kFreeStaggerSlice = 16;
-constexpr long kFreeStaggerDelay = 49000, kFreeStaggerDelayMax = 1 << 20;
+// RolloutFreeArgs::prio: the paced acting (wait after acting 9.0k -> 4.5k cycles, 47.07 -> 46.66 us per round against
+// waves 4.. at raised priority for the whole acting, profiles/r7; that 49.6 -> 49.0 against none, profiles/r7c)
+constexpr int kFreePrio = 4, kFreeSeparate = 1;
 template <class SH>
 static hipError_t launch_rollout_free_sh(const Params& P, int64_t E, uint8_t* recs, uint32_t* mt, Liab* liab,
                                          const StepIO& io, const FusedActFree& fa, const RoundStrideFree& st,
                                          int n_rounds, int act_last, hipStream_t s) {
     const int64_t epb = (int64_t)kFreeEPW * P.N;
     const int64_t blocks = (E + epb - 1) / epb;
-    static const int prio = [] {
-        const char* v = getenv("MS_FREE_PRIO");  // (measurement knob, tools/gpu_job.sh envab)
-        // measured: 1 (acting) 49.6 -> 49.0 us per round, 3 (and env) 49.1 (profiles/r7c); 4 (paced acting)
-        // 47.07 -> 46.66 us against 1 over three A/B pairs, wait after acting 9.0k -> 4.5k cycles (profiles/r7)
-        return v ? atoi(v) : 4;
-    }();
-    // MS_FREE_STAGGER (read at every launch; a captured launch keeps what it was captured with): 0 the plain
-    // kernel, 1 the rank-1 workgroup of a CU starts MS_FREE_STAGGER_DELAY cycles late, 2 the two workgroups
-    // apart by issue priority, 3 both, 4 / 5 as 2 / 3 with the higher priority going to the two workgroups in
-    // turns (slices of 2^MS_FREE_STAGGER_SLICE ticks of the 100 MHz clock)
+    // MS_FREE_STAGGER=0 (read at every launch; a captured launch keeps what it was captured with): the plain
+    // kernel, the tests' reference. Otherwise the staggered one (17.26 -> 16.48 ms per cfg3 iteration,
+    // profiles/r10a).
     const char* sv = getenv("MS_FREE_STAGGER");
-    const int stagger = sv ? atoi(sv) & 7 : kFreeStaggerDefault;
-    const char* lv = getenv("MS_FREE_STAGGER_SLICE");
-    const int slice = lv ? atoi(lv) & 31 : kFreeStaggerSlice;
-    const char* dv = getenv("MS_FREE_STAGGER_DELAY");
-    long delay = dv ? atol(dv) : kFreeStaggerDelay;
-    delay = delay < 0 ? 0 : (delay > kFreeStaggerDelayMax ? kFreeStaggerDelayMax : delay);
-    const RolloutFreeArgs A{P, E, recs, mt, liab, io, fa, st, n_rounds, act_last, prio, stagger, (int)delay, slice};
+    const bool stagger = !(sv && strcmp(sv, "0") == 0);
+    const RolloutFreeArgs A{P, E, recs, mt, liab, io, fa, st, n_rounds, act_last, kFreePrio, kFreeSeparate};
     auto kern = stagger ? (io.metrics ? k_env_rollout_act_free<SH, true, true> : k_env_rollout_act_free<SH, false, true>)
                         : (io.metrics ? k_env_rollout_act_free<SH, true> : k_env_rollout_act_free<SH, false>);
     hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(64 * P.N), (size_t)free_lds(P).total, s, A);
     return hipGetLastError();
-}
-// quads with owned items stored whole, merged with the values the rollout wrote: every line of the outputs is
-// written whole (the per-item stores left every line partial): 501 -> 425 us per 199-round fill (profiles/r7s).
-// MS_FILL_MERGE=0: the per-item stores (A/B measurements)
-static int fill_merge() {
-    static const int v = [] {
-        const char* e = getenv("MS_FILL_MERGE");
-        return e && e[0] == '0' ? 0 : 1;
-    }();
-    return v;
-}
-// MS_FILL_PAIR=0: the quad fill without the draw pairing (A/B measurements)
-static bool fill_pair_enabled() {
-    static const bool v = [] {
-        const char* e = getenv("MS_FILL_PAIR");
-        return !(e && e[0] == '0');
-    }();
-    return v;
-}
-// MS_FILL_QUAD=0: the per-item fill kernel (A/B measurements)
-static bool fill_quad_enabled() {
-    static const bool v = [] {
-        const char* e = getenv("MS_FILL_QUAD");
-        return !(e && e[0] == '0');
-    }();
-    return v;
 }
 // where the fill kernels read the agents' common-row tables in an acceptor act fragment block (FragLayout<2, 2>,
 // ms_act_prepare with a common row): agent 0's table and the dwords between two agents' tables. The PPO
@@ -3126,7 +3069,7 @@ hipError_t launch_env_fill_common(const Params& P, int64_t E, const StepIO& io, 
                            (uint32_t)fa.acc.row_base, fa.seed, fa.acc_offset, st.offset_step, fa.offset_dev};
     const int64_t items = E * P.N * P.C;
     // the quad kernel: C % 4 == 0 and every round's owners / actions 4-byte, log-probs 16-byte aligned
-    const bool quad = P.C % 4 == 0 && fill_quad_enabled() &&
+    const bool quad = P.C % 4 == 0 &&
                       ((reinterpret_cast<uintptr_t>(c.owner) | (uintptr_t)c.owner_stride) & 3) == 0 &&
                       ((reinterpret_cast<uintptr_t>(c.action) | (uintptr_t)c.action_stride) & 3) == 0 &&
                       ((reinterpret_cast<uintptr_t>(c.logprob) | (uintptr_t)c.logprob_stride) & 15) == 0 &&
@@ -3135,13 +3078,13 @@ hipError_t launch_env_fill_common(const Params& P, int64_t E, const StepIO& io, 
     if (quad) {
         const unsigned by = (unsigned)((n_acts + kFillRounds - 1) / kFillRounds);
         const int64_t qr = (int64_t)P.N * P.C / 4;
-        if (64 % P.C == 0 && fill_pair_enabled()) {  // threads: quads of the replicas e with e & (64 / C) == 0
+        if (64 % P.C == 0) {  // threads: quads of the replicas e with e & (64 / C) == 0
             const int64_t S = 64 / P.C, pairs = (E + 2 * S - 1) / (2 * S) * S;
             hipLaunchKernelGGL(k_acc_common_fill4<true>, dim3((unsigned)((pairs * qr + 255) / 256), by), dim3(256), 0, s,
-                               c, n_acts, fill_merge());
+                               c, n_acts);
         } else {
             hipLaunchKernelGGL(k_acc_common_fill4<false>, dim3((unsigned)((E * qr + 255) / 256), by), dim3(256), 0, s, c,
-                               n_acts, fill_merge());
+                               n_acts);
         }
         return hipGetLastError();
     }

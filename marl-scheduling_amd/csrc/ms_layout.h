@@ -236,7 +236,7 @@ inline constexpr FreeLds free_lds(const Geom& g) {
     // (by-core mode) the replicas' acceptor actions [kFreeEPW * N][N * C]: the acting writes its owned items, the
     // next env round stages its owners' from here (outside the wave slots the MT refill may overwrite)
     f.pace = f.accx + align4(kFreeEPW * g.N * g.N * g.C);
-    f.total = f.pace + 4 * 8;  // (MS_FREE_PRIO bit 2) each wave's count of acting steps done
+    f.total = f.pace + 4 * 8;  // (act_free's pace) each wave's count of acting steps done
     return f;
 }
 // The shapes k_env_rollout_act_free is built for (env_rollout_free_supported): 16 lanes per replica

@@ -1862,15 +1862,6 @@ static hipError_t launch_own(const PpoArgs& a, unsigned nb, hipStream_t st) {
     return launch_grad_cm<NQ, NT, kMaskRow | X>(a, nb, st);
 }
 
-// MS_KEY_GATHER_ROWS=0: the per-lane gather for every layout (A/B measurements)
-static bool gather_per_row() {
-    static const bool v = [] {
-        const char* e = getenv("MS_KEY_GATHER_ROWS");
-        return e && e[0] == '0';
-    }();
-    return v;
-}
-
 // the common-row path for inputs up to 128 bytes (its scan holds a row per lane in registers)
 // X = kX1: the tile path with a single-action last tile (A = 16 (NT - 1) + 1); the keyed passes never take it
 template <int NQ, int NT, int X = 0>
@@ -1891,8 +1882,7 @@ static hipError_t launch_grad_t(const PpoArgs& a0, hipStream_t st) {
                 if ((e = hipGetLastError()) != hipSuccess) return e;
             }
             const unsigned ib = (unsigned)std::min<long long>((a.R + 255) / 256, 16384);
-            if (a.rus == 1 && a.rrs <= 64 && (a.rrs & 3) == 0 && a.ret_ld <= 64 && a.ret_ld >= a.G &&
-                !gather_per_row()) {
+            if (a.rus == 1 && a.rrs <= 64 && (a.rrs & 3) == 0 && a.ret_ld <= 64 && a.ret_ld >= a.G) {
                 const size_t lds = (size_t)kGatherWaves * 64 * (std::max<long long>(a.rrs, a.ret_ld) + 1) * 4;
                 hipLaunchKernelGGL(k_key_gather_rows, dim3(ib), dim3(64 * kGatherWaves), lds, st, a);
             } else {
@@ -1932,15 +1922,6 @@ static hipError_t launch_grad_t(const PpoArgs& a0, hipStream_t st) {
     return launch_grad_cm<NQ, NT, kPlain | X>(a, nb, st);
 }
 
-// MS_GRAD_X1=0: single-action last tiles on the MFMA like the others (A/B measurements)
-static bool grad_x1_enabled() {
-    static const bool v = [] {
-        const char* e = getenv("MS_GRAD_X1");
-        return !(e && e[0] == '0');
-    }();
-    return v;
-}
-
 // partial vectors per group that launch_ppo_grad writes (the keyed path adds its slot blocks)
 int ppo_partial_rows(int n_chunks, bool keyed) { return n_chunks / 4 + (keyed ? kKeyBlocks : 0); }
 
@@ -1957,7 +1938,7 @@ hipError_t launch_ppo_grad(const PpoArgs& a, const GradOut& go, hipStream_t st) 
     }
     // A = 16 (nt - 1) + 1 at the BASELINE shapes that have it (cfg4: offers C + 1 = 17 with 16 < D + 1 <= 64,
     // divided acceptors O + 1 = 49 with 64 < D + 1 <= 128)
-    if (a.A % 16 == 1 && !keyed && grad_x1_enabled()) {
+    if (a.A % 16 == 1 && !keyed) {
         if (nt == 2 && nq > 2 && nq <= 4) {
             e = launch_grad_t<4, 2, kX1>(a, st);
             goto reduce;

@@ -221,8 +221,6 @@ class Trainer:
             self.price = _Unit("price", self.E, T, N * L, (N * L) // go, 4, 4, s.price_actions,
                                mk(go, 4, s.price_actions, hp.offer_gamma, k_off, nets["price"]), dev, torch.float32,
                                unit_major=self.price_unit_major)
-        if self.free and os.environ.get("MS_PRICE_KEYED", "1") == "0":
-            self.price.group.row_keys = 1  # the price chooser's gradient on the tile path (A/B measurements)
         if world_size > 1:
             self._broadcast_params()
         # A single net's item i takes word (i >> 6) & 1 of the draw countered by item i & ~64 (k_act_common's rule on
@@ -267,10 +265,8 @@ class Trainer:
         self.acc_common = torch.tensor(crow, dtype=torch.int8, device=dev)
         # the acting nets' weight fragments (and the acceptors' common-row table), rebuilt at the start
         # of every rollout like the price table (ActFrag; bit-identical to acting without them)
-        # (MS_ACT_FRAG=0: without them, for A/B measurements)
-        use_frag = os.environ.get("MS_ACT_FRAG", "1") != "0"
-        self.off_frag = ActFrag(self.off.group.policy_old, s.off_obs_stride) if use_frag else None
-        self.acc_frag = ActFrag(self.acc.group.policy_old, s.acc_obs_stride, self.acc_common) if use_frag else None
+        self.off_frag = ActFrag(self.off.group.policy_old, s.off_obs_stride)
+        self.acc_frag = ActFrag(self.acc.group.policy_old, s.acc_obs_stride, self.acc_common)
         self.agent_reward = torch.zeros((self.E, N), dtype=torch.int32, device=dev)
         self.auct_reward = torch.zeros((self.E, C), dtype=torch.int32, device=dev)
         self.rng = random.Random(seed)  # sub-unit draws (random.randint), identical on every rank
@@ -304,7 +300,7 @@ class Trainer:
         # (MS_ENV_FUSED_ACT=0: the act launch and the env launch of every round, for A/B measurements)
         # (T > 1: the fused acting writes round t + 1's ring slots)
         self.fused_step = (self.compact and not self.free and self.acc.group.policy.G == 1 and
-                           self.off.group.policy.G == 1 and self.acc_frag is not None and self.T > 1 and
+                           self.off.group.policy.G == 1 and self.T > 1 and
                            os.environ.get("MS_ENV_FUSED_ACT", "1") != "0" and fused_metrics_ok and
                            all(env.fused_act_supported() for env, _, _ in self.env.parts))
         # ... and the whole rollout's rounds are one launch (ms_env_rollout_act): each wave steps and acts
@@ -314,16 +310,13 @@ class Trainer:
         # a workgroup steps its replicas, then acts for them with one wave per agent, round after round
         # (MS_ENV_ROLLOUT_FREE=0: an act launch and an env launch per round, for A/B measurements)
         self.fused_rollout_free = (self.compact and self.free and arch == "local" and self.price_table is not None and
-                                   self.off_frag is not None and not self.price_unit_major and self.T > 1 and
-                                   fused_metrics_ok and os.environ.get("MS_ENV_ROLLOUT_FREE", "1") != "0" and
+                                   not self.price_unit_major and self.T > 1 and fused_metrics_ok and
+                                   os.environ.get("MS_ENV_ROLLOUT_FREE", "1") != "0" and
                                    all(env.rollout_free_supported() for env, _, _ in self.env.parts))
         # ... and its acceptor items of cores their agent does not own (sampled from the common row's table; the env
         # reads only the owner's acceptor action) are left to a second kernel (ms_env_rollout_fill_common) after the
-        # launch. MS_DEFER_COMMON=1: iteration() runs it inside the update instead, on the acceptor's stream beside
-        # the offer and price gradients (offsets from a snapshot of rng_ctr taken by the rollout); measured even
-        # (17.84-17.92 ms per iteration either way, profiles/r7: the update is as throughput-bound as the rollout)
-        self.defer_common = (self.fused_rollout_free and self.update_streams and self.world_size == 1 and self.fused and
-                             os.environ.get("MS_DEFER_COMMON", "0") == "1")
+        # launch. (Running it inside the update instead, on the acceptor's stream beside the offer and price
+        # gradients, measured even: 17.84-17.92 ms per iteration either way, profiles/r7.)
         self.rng_snap = torch.zeros(1, dtype=torch.int64, device=self.device)
         # the rollout's owned acceptor items by core ([T][E][C]; ABI 18): the fill then writes the acceptor rings'
         # rows whole (MS_FILL_OWN=0: the rollout writes them into the rings, one item in eight of a line)
@@ -335,11 +328,9 @@ class Trainer:
         # the rollout always leaves them, iteration() never runs the fill, and whoever reads the acceptor rings
         # afterwards (acc.actions / acc.logprobs) gets them completed by one eager fill (_complete_rings).
         # One replica part only (the fill's arguments and the row base are one part's); any world size.
-        # MS_ACC_REGEN=0: the fill after the rollout and a gradient that reads the rings (A/B runs, equality tests);
-        # so does MS_DEFER_COMMON=1 (the fill moved into the update, where the gradient then reads the rings)
+        # MS_ACC_REGEN=0: the fill after the rollout and a gradient that reads the rings (A/B runs, equality tests)
         self.acc_regen = (self.fused_rollout_free and self.acc_own is not None and self.fused and
-                          rollout_streams == 1 and ABI_LOADED >= 20 and not self.defer_common and
-                          os.environ.get("MS_ACC_REGEN", "1") != "0")
+                          rollout_streams == 1 and ABI_LOADED >= 20 and os.environ.get("MS_ACC_REGEN", "1") != "0")
         if self.acc_regen:
             self.acc.complete = self._complete_rings
         self._rings_pending = False
@@ -393,9 +384,8 @@ class Trainer:
         self._complete_rings()  # a pending fill samples from the tables about to be rebuilt
         if self.price_table is not None:
             self.price_table.build(self.price.group.policy_old)
-        if self.off_frag is not None:
-            self.off_frag.build(self.off.group.policy_old)
-            self.acc_frag.build(self.acc.group.policy_old)
+        self.off_frag.build(self.off.group.policy_old)
+        self.acc_frag.build(self.acc.group.policy_old)
         self._acting_version = self._policy_version
 
     def round(self, t: int):
@@ -570,10 +560,10 @@ class Trainer:
         if self.acc_own is not None:
             strides.next_own_action, strides.next_own_logprob = b(self.acc_own[0]), b(self.acc_own[1])
         nxt, out = self._fused_next_free(1, k)
-        nxt.defer_common = int(self.defer_common or self.acc_regen)
+        nxt.defer_common = int(self.acc_regen)
         env.rollout_act_free(sl(self.acc.actions[0]).view(E, N, C), sl(self.off.actions[0]).view(E, N, L), obs, rew,
                              nxt, out, strides, self.T, act_after_last=False, events=ev, stream=self.streams[k])
-        if self.defer_common or self.acc_regen:
+        if self.acc_regen:
             # the fill's arguments: the same call with the offsets of this rollout (snapshot). It reads the owners
             # of ring slots >= 1 (_carry_last_observation rewrites slot 0 only) and the acceptor tables of
             # this rollout (_prepare_acting completes pending rings before it rebuilds them)
@@ -583,7 +573,7 @@ class Trainer:
             self._fill_args.append((env, obs, fill, strides))
 
     def fill_common(self, stream=None):
-        """The deferred acceptor items of the last one-launch rollout (defer_common / acc_regen; idempotent)."""
+        """The deferred acceptor items of the last one-launch rollout (acc_regen; idempotent)."""
         for env, obs, fill, strides in self._fill_args:
             env.fill_common(obs, fill, strides, self.T, act_after_last=False, stream=stream)
 
@@ -649,7 +639,7 @@ class Trainer:
             self.spans.zero_()
         self._prepare_acting()
         self._fill_args = []
-        if self.defer_common or self.acc_regen:
+        if self.acc_regen:
             self.rng_snap.copy_(self.rng_ctr)
         for s in self.streams[1:]:  # fork: the side streams start after everything queued so far
             s.wait_stream(cur)
@@ -667,8 +657,8 @@ class Trainer:
     def rollout(self, defer_common: bool = False):
         """UPDATE_STEP rounds. With use_graph the first rollout runs eagerly and is then
         captured once into a HIP graph (every pointer is static); later rollouts replay it.
-        defer_common (iteration()): leave the deferred acceptor items (self.defer_common) to the update, which
-        samples them on the acceptor's stream; otherwise the rings are complete when this returns."""
+        defer_common (iteration(); acc_regen only): leave the pending acceptor rings to be completed at their
+        first read (_complete_rings); otherwise the rings are complete when this returns."""
         self._rings_pending = False  # (rings of an earlier rollout nobody read: overwritten now)
         if not self.use_graph:
             self._rollout_body()
@@ -685,8 +675,6 @@ class Trainer:
             self._rings_pending = True
             if not defer_common:
                 self._complete_rings()
-        elif self.defer_common and not defer_common:
-            self.fill_common()
         self.rounds_done += self.T
 
     # ---- update
@@ -835,32 +823,12 @@ class Trainer:
     def _fused_phases(self, all_sel, counts, out):
         """_fused_update as a generator: yields the parameters whose gradients the ranks all-reduce
         (several ranks only) and leaves the losses in out["losses"]."""
-        T, E = self.T, self.E
         losses = {}
-        if self.defer_common:  # the rollout's deferred acceptor items (a trainer switched to several ranks)
-            self.fill_common()
         # Each unit type's draws update its nets in sequence (draw d trains on the weights draw d-1
         # left), but the unit types are independent nets: step s of the update = epoch k of draw d
         # of every unit type that has one, with ONE all-reduce of all their gradients (one
         # flattened RCCL call per step, DESIGN §7) before each type's Adam step.
-        steps = {}
-        for u in self.units():
-            # the returns of every draw's sub-units in one launch: [T][E][sum of G], draw d at
-            # column offset d*G (returns depend on the rewards only, not on earlier draws' updates)
-            sel_u = all_sel[u.name]
-            ret_all = unit_returns(u.rewards, sel_u, u.group.gamma)
-            common = self.acc_common if (u is self.acc and self.common_rows) else None
-            owner = self.acc_owner[:T].reshape(T * E, self.C) if (u is self.acc and self.compact) else None
-            regen = self._acc_regen_args() if (u is self.acc and self.acc_regen) else None
-            col, seq = 0, []
-            rows = self._update_rows(u)
-            for n in counts[u.name]:
-                ep = u.group.fused_epoch(*rows, ret_all.view(-1)[col:], sel_u[col:col + n], T, E, common_row=common,
-                                         returns_ld=sel_u.numel(), core_owner=owner, unit_major=u.unit_major,
-                                         regen=regen)
-                seq += [ep] * u.group.K
-                col += n
-            steps[u.name] = (u, seq, [])
+        steps = {u.name: (u, self._epochs(u, all_sel[u.name], counts[u.name]), []) for u in self.units()}
         # each unit type's loss terms of every (draw, epoch) into one [n][G][3] buffer, combined once at the end
         terms = {name: torch.empty((len(seq), u.group.policy.G, 3), dtype=torch.float32, device=self.device)
                  for name, (u, seq, _) in steps.items()}
@@ -910,8 +878,6 @@ class Trainer:
             st.wait_stream(cur)
         for u, st in zip(units, self._unit_streams):
             with torch.cuda.stream(st):
-                if u is self.acc and self.defer_common:
-                    self.fill_common(stream=st)  # the rollout's deferred acceptor items, beside the other units
                 seq = self._epochs(u, all_sel[u.name], counts[u.name])
                 # every (draw, epoch)'s loss terms into one buffer, combined at once (not four small kernels each)
                 terms = torch.empty((len(seq), u.group.policy.G, 3), dtype=torch.float32, device=self.device)
@@ -930,8 +896,6 @@ class Trainer:
         """The torch-autograd update (the numerical reference of the fused one)."""
         T = self.T
         losses = {}
-        if self.defer_common:
-            self.fill_common()
         for u in self.units():
             ls = []
             st_u = self.acceptor_rows(0, T) if (u is self.acc and self.compact) else self._states_of(u)

@@ -75,11 +75,12 @@ def test_cfg3_one_launch_rollout_equals_two_launches(ms, monkeypatch, E, T, own)
     _compare(trs)
 
 
-@pytest.mark.parametrize("N,C,L,E", [(6, 6, 3, 500), (8, 7, 2, 256), (4, 9, 4, 130)])
+@pytest.mark.parametrize("N,C,L,E", [(6, 6, 3, 500), (8, 7, 2, 256), (4, 9, 4, 130), (4, 12, 4, 130)])
 def test_generic_shape_one_launch_rollout_equals_two_launches(ms, monkeypatch, N, C, L, E):
     """Other locally shared free-price shapes run the DynShape kernel (6 x 6 x 3: 6 waves per workgroup;
     8 x 7 x 2: 2C = 14, the slot pair inside a template dword; 4 x 9 x 4: 144 acceptor items per workgroup, so
-    the 64-item draw pairing is not aligned to the workgroups): equal to the two launches."""
+    the 64-item draw pairing is not aligned to the workgroups; 4 x 12 x 4: C % 4 == 0 with 64 % C != 0, the
+    common-item fill by quads without the draw pairing, k_acc_common_fill4<false>): equal to the two launches."""
     abi = importlib.import_module("marl-scheduling_amd.abi")
     tr_mod = importlib.import_module("marl-scheduling_amd.trainer")
     cfg = abi.make_config(N, C, L, free_prices=True, commercial=True, **abi.EXP4_JOBS)
@@ -174,18 +175,15 @@ def test_one_round_rollouts(ms, name):
 def test_update_streams_equal_one_stream(ms, monkeypatch, name, E):
     """One rank updates each unit type on its own stream by default (Trainer.update_streams; the unit types are
     independent nets, PPOmodules.py:548-597): every loss and weight equals the one-stream update's bit for bit,
-    over three iterations (each acting on the previous update's weights), graph-replayed. cfg3's trainer with
-    streams also defers (MS_DEFER_COMMON=1) the rollout's common acceptor items into the update: every ring equals the
+    over three iterations (each acting on the previous update's weights), graph-replayed. Every ring equals the
     one-stream trainer's after each iteration."""
     tr_mod = importlib.import_module("marl-scheduling_amd.trainer")
     ppo = importlib.import_module("marl-scheduling_amd.ppo")
     mk = lambda: tr_mod.Trainer.from_named(name, n_envs=E, update_step=12, seed=6, device="cuda:0")
-    monkeypatch.setenv("MS_DEFER_COMMON", "1")
     streams = mk()
     monkeypatch.setenv("MS_UPDATE_STREAMS", "0")
     one = mk()
     assert streams.update_streams and not one.update_streams
-    assert streams.defer_common == (name == "cfg3") and not one.defer_common
     for it in range(3):
         l0, l1 = streams.iteration(), one.iteration()
         torch.cuda.synchronize()

@@ -151,19 +151,19 @@ def test_cfg3_one_launch_metrics_of_parts(ms, monkeypatch):
 
 
 def test_cfg3_metrics_with_deferred_common_fill(ms, monkeypatch):
-    """MS_DEFER_COMMON=1 (the common acceptor items sampled inside the update, no regenerating gradient) with
-    metrics, through iteration() as a training run calls it (graph replay, harvest inside): episode logs,
+    """MS_ACC_REGEN=0 (the common acceptor items sampled by the fill after the rollout launch, no regenerating
+    gradient) with metrics, through iteration() as a training run calls it (graph replay, harvest inside): episode logs,
     the accumulators of the unfinished episode, rings and losses equal the launch-per-round trainer's."""
     tr_mod = importlib.import_module("marl-scheduling_amd.trainer")
     mk = lambda: tr_mod.Trainer.from_named("cfg3", n_envs=64, update_step=20, seed=3, device="cuda:0", metrics=True,
                                            episode_length=EP_LEN)
-    monkeypatch.setenv("MS_DEFER_COMMON", "1")
+    monkeypatch.setenv("MS_ACC_REGEN", "0")
     fused = mk()
-    monkeypatch.delenv("MS_DEFER_COMMON")
+    monkeypatch.delenv("MS_ACC_REGEN")
     monkeypatch.setenv("MS_ROLLOUT_METRICS", "0")
     plain = mk()
     monkeypatch.delenv("MS_ROLLOUT_METRICS")
-    assert fused.fused_rollout_free and fused.defer_common and not fused.acc_regen and not plain.fused_rollout_free
+    assert fused.fused_rollout_free and not fused.acc_regen and not plain.fused_rollout_free
     for it in range(3):
         l0, l1 = fused.iteration(), plain.iteration()
         torch.cuda.synchronize()

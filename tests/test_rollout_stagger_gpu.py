@@ -1,16 +1,15 @@
 """MS_FREE_STAGGER: the two workgroups of a CU told apart in the one-launch free-price rollout
-(k_env_rollout_act_free's STAG kernels, env_kernels.hip; mode 4 is the default).
+(k_env_rollout_act_free's STAG kernels, env_kernels.hip; the default, and what every value but 0 selects).
 
-A workgroup's rank on its CU (the parity of a ticket it takes once per launch) changes only when it runs: a start
-delay for rank 1 (bit 0) and the issue priorities of the two phases, by rank (bit 1) or by rank and clock slice
-(bit 2). No workgroup reads what another
-wrote, so every mode must give the bytes of MS_FREE_STAGGER=0: every ring, the owned acceptor items, the losses,
+A workgroup's rank on its CU (the parity of a ticket it takes once per launch) changes only when it runs: the issue
+priorities of the two phases, by rank and clock slice. No workgroup reads what another
+wrote, so every value must give the bytes of MS_FREE_STAGGER=0: every ring, the owned acceptor items, the losses,
 the weights, the exported env state and the flags, over two iterations of a fresh trainer. The variable is read at
 every launch (and kept by a captured launch), so each trainer lives inside its own setting.
 
 The shapes: three workgroups (CUs with one workgroup, whose rank meets no partner), a partial last workgroup, more
 workgroups than the device holds at once (late arrivals take tickets on CUs that already gave two), the DynShape
-kernel, the metrics kernel, and a launch of one round, which has no acting at all: the delay has to end by itself.
+kernel, the metrics kernel, and a launch of one round, which has no acting at all.
 The reference of a case is computed once and shared by its modes."""
 import ctypes as ct
 import importlib
@@ -21,7 +20,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
-MODES = (1, 2, 3, 4, 5)  # (4, 5: 2, 3 with the priority pairs taken in turns by the clock)
+MODES = (1, 2, 3, 4, 5)  # (once five modes, now five spellings of "not 0": each must select the staggered kernels)
 
 
 def _mod(name):
@@ -133,7 +132,7 @@ def test_stagger_modes_equal_the_plain_launch(ms, monkeypatch, case, mode):
 
 
 def test_ticket_parity_carries_over_launches(ms, monkeypatch):
-    """Mode 3 twice in one process: the second trainer's launches start from whatever tickets the first left."""
+    """The staggered launch (value 3, as good as any but 0) twice in one process: the second trainer's launches start from whatever tickets the first left."""
     monkeypatch.setenv("MS_FREE_STAGGER", "3")
     a, _ = _run(CASES["three_workgroups"])
     b, _ = _run(CASES["three_workgroups"])
@@ -174,8 +173,8 @@ def _one_round(E):
 
 
 def test_one_round_without_acting(ms, monkeypatch):
-    """T = 1: the launch has no barrier after its env round and no acting; the delayed workgroups still end, and
-    the round's outputs are those of the plain launch."""
+    """T = 1: the launch has no barrier after its env round and no acting; the
+    round's outputs are those of the plain launch."""
     monkeypatch.setenv("MS_FREE_STAGGER", "0")
     ref = _one_round(96)
     for mode in MODES:

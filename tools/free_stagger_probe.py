@@ -11,8 +11,8 @@ last rollout launch is reported:
   - the round length and the rollout's time (of the probe build: its stamps cost a little).
 
 Usage: python tools/free_stagger_probe.py [--envs E] [--rounds T] SETTING ...
-  SETTING is MODE or MODE:DELAY (MS_FREE_STAGGER and MS_FREE_STAGGER_DELAY), e.g. 0 1:49000 2 3:49000 4;
-  MS_FREE_STAGGER_SLICE is taken from the environment. MARLSCHED_LIB names another probe build."""
+  SETTING is MS_FREE_STAGGER's value: 0 (the plain kernels) or 1 (the staggered ones, the default).
+  MARLSCHED_LIB names another probe build."""
 import argparse
 import ctypes as ct
 import importlib
@@ -84,20 +84,15 @@ def main():
     ap.add_argument("--envs", type=int, default=16384)
     ap.add_argument("--rounds", type=int, default=200)
     ap.add_argument("--iters", type=int, default=4)
-    ap.add_argument("settings", nargs="+")
+    ap.add_argument("settings", nargs="+", choices=("0", "1"))
     a = ap.parse_args()
     import torch
     tr_mod = importlib.import_module("marl-scheduling_amd.trainer")
     lib = importlib.import_module("marl-scheduling_amd._lib").lib
     lib.ms_probe_free_rounds.argtypes = [ct.POINTER(ct.c_ulonglong), ct.c_int]
     n_cus = torch.cuda.get_device_properties(0).multi_processor_count
-    for s in a.settings:
-        mode, _, delay = s.partition(":")
+    for mode in a.settings:
         os.environ["MS_FREE_STAGGER"] = mode
-        if delay:
-            os.environ["MS_FREE_STAGGER_DELAY"] = delay
-        else:
-            os.environ.pop("MS_FREE_STAGGER_DELAY", None)
         tr = tr_mod.Trainer.from_named("cfg3", n_envs=a.envs, update_step=a.rounds, seed=0, device="cuda:0")
         assert tr.fused_rollout_free and len(tr.env.parts) == 1
         wgs = -(-a.envs // (4 * tr.N))
@@ -114,8 +109,7 @@ def main():
         assert lib.ms_probe_free_rounds(buf, wgs) == 0
         raw = np.frombuffer(buf, dtype=np.uint64).reshape(wgs, W)
         lines = analyse(raw, a.rounds, n_cus)
-        print("== MS_FREE_STAGGER=%s%s  E %d  T %d" % (mode, " MS_FREE_STAGGER_DELAY=" + delay if delay else "", a.envs,
-                                                       a.rounds))
+        print("== MS_FREE_STAGGER=%s  E %d  T %d" % (mode, a.envs, a.rounds))
         print("rollout (probe build, graph replays): " + " ".join("%.3f" % x for x in ms[2:]) + " ms")
         print("\n".join(lines))
         sys.stdout.flush()
