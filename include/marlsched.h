@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define MS_ABI_VERSION 21
+#define MS_ABI_VERSION 22
 
 #define MS_MAX_KINDS 16
 #define MS_MAX_AGENTS 64
@@ -278,6 +278,33 @@ int ms_env_set_rng(ms_env* env, int64_t env_index, const uint32_t* words, int32_
  * the reference invariants the kernel relies on. */
 int ms_env_export(ms_env* env, const ms_state_host* out, void* stream);
 int ms_env_import(ms_env* env, const ms_state_host* in, void* stream);
+
+/* ---- packed snapshot (ABI 22): the env's whole state in one caller-owned device buffer, for checkpoints.
+ * Little-endian, every section 16-byte aligned (csrc/ms_snapshot.h holds the offsets and the check):
+ *   header    64 B: u32 magic "MSSP", u32 layout version (1), i64 E, i32 N, C, L, cap, rec_bytes,
+ *             sizeof(ms_config), i64 n_liab (live liability entries of all replicas), u64 total_bytes, 8 B zero
+ *   config    the env's ms_config bytes (struct padding zeroed), padded to 16
+ *   recs      [E][rec_bytes] the records as they are (round, flags and mti kept), header dword 3 (which MT
+ *             half is current) written as 0
+ *   mt        [E][624] u32: the current MT19937 block of every replica, the words random.getstate() returns
+ *   liab_off  [E + 1] u64: exclusive prefix sum over replicas of their live entries, padded to 16
+ *   liab      [n_liab] x 8 B {i8 offerer, recipient, price, nec_time; i32 round}: within a replica core-major,
+ *             oldest to newest; padded to 16
+ * so total_bytes = align16(64 + sizeof(ms_config)) + E * (rec_bytes + 2496) + align16(8 * (E + 1)) +
+ * align16(8 * n_liab). The successor MT block and the chain slots beyond liab_n are left out: at cfg3 a
+ * snapshot is about a fifth of the device state. Equal states give equal bytes.
+ *
+ * ms_env_snapshot packs the state into dev_buf (device memory, 16-byte aligned, cap_bytes long). Synchronous.
+ * *used_bytes gets the snapshot's size; dev_buf == NULL only computes it. cap_bytes too small: MS_EINVAL,
+ * *used_bytes = the size needed.
+ * ms_env_restore validates dev_buf[0, bytes) against this env (shape, config, E, the sizes, and per replica
+ * every invariant ms_env_import checks plus its liab_off span), then replaces the env's state with it, as
+ * ms_env_import does: the round counter from replica 0, the sticky error word set when a restored record
+ * carries a fatal flag, the MT block as half 0 (the device recomputes its successor before the replica's next
+ * draw). Synchronous. A refused snapshot (MS_EINVAL, ms_last_error names the replica and the field) leaves the
+ * env exactly as it was; whatever the buffer holds, nothing outside [dev_buf, dev_buf + bytes) is read. */
+int ms_env_snapshot(ms_env* env, void* dev_buf, size_t cap_bytes, size_t* used_bytes, void* stream);
+int ms_env_restore(ms_env* env, const void* dev_buf, size_t bytes, void* stream);
 
 /* ---- policy act: fused Linear-tanh-Linear-tanh-Linear-softmax + Categorical ----
  * Rows: obs[e][u][stride] int8 for e < n_envs, u < n_units. Unit u uses weight

@@ -27,7 +27,7 @@ class MarlSchedError(RuntimeError):
         self.code = code
 
 
-ABI_VERSION = 21  # include/marlsched.h MS_ABI_VERSION
+ABI_VERSION = 22  # include/marlsched.h MS_ABI_VERSION
 
 
 def _load():
@@ -71,6 +71,8 @@ def _load():
         "ms_env_set_rng": (ct.c_int, [P, i64, ct.POINTER(u32), i32, P]),
         "ms_env_export": (ct.c_int, [P, ct.POINTER(abi.MsStateHost), P]),
         "ms_env_import": (ct.c_int, [P, ct.POINTER(abi.MsStateHost), P]),
+        "ms_env_snapshot": (ct.c_int, [P, P, ct.c_size_t, ct.POINTER(ct.c_size_t), P]),
+        "ms_env_restore": (ct.c_int, [P, P, ct.c_size_t, P]),
         "ms_policy_act": (ct.c_int, [ct.POINTER(abi.MsMlpParams), P, i32, i64, i32, i32, u64, u64, P, P, P, P, P]),
         "ms_policy_act_common": (ct.c_int, [ct.POINTER(abi.MsMlpParams), P, i32, i64, i32, i32, P, u64, u64, P, P, P,
                                             P, P]),
@@ -134,16 +136,18 @@ def _load():
     # (ms_policy_act_greedy, ms_act_round_greedy), 20 ms_ppo_batch's regen fields (trailing fields an older library
     # does not read: the trainer passes them from ABI 20 on only), 21 episode metrics inside ms_env_step_act /
     # ms_env_rollout_act / ms_env_rollout_act_free (an older library refuses them: the trainer then keeps the
-    # launch-per-round path under metrics). An older library (an A/B variant built before them,
+    # launch-per-round path under metrics), 22 the packed env snapshot (ms_env_snapshot / ms_env_restore: an older
+    # library has no checkpoints). An older library (an A/B variant built before them,
     # tools/gpu_job.sh ab step) loads without them only when MARLSCHED_LENIENT_ABI=1 asks for it
-    lenient = os.environ.get("MARLSCHED_LENIENT_ABI") == "1" and version in (13, 14, 15, 16, 17, 18, 19, 20, 21)
+    lenient = os.environ.get("MARLSCHED_LENIENT_ABI") == "1" and version in (13, 14, 15, 16, 17, 18, 19, 20, 21, 22)
     if version != ABI_VERSION and not lenient:
         raise ImportError("libmarlsched.so ABI version mismatch (%d, want %d)" % (version, ABI_VERSION))
     for name, (res, args) in sig.items():
         if (version < 14 and name.startswith("ms_bdqn_update")) or (version < 15 and name == "ms_bdqn_act_compact") \
                 or (version < 16 and (name.startswith("ms_env_step_act") or name == "ms_env_rollout_act")) \
                 or (version < 17 and name.startswith("ms_env_rollout_act_free")) \
-                or (version < 19 and name.endswith("_greedy")):
+                or (version < 19 and name.endswith("_greedy")) \
+                or (version < 22 and name in ("ms_env_snapshot", "ms_env_restore")):
             continue
         if lenient and not hasattr(L, name):  # an older build of this ABI (A/B variants)
             continue
@@ -168,7 +172,7 @@ EXPORTED = (
     "ms_env_reset", "ms_env_step", "ms_env_step_act", "ms_env_step_act_supported", "ms_env_rollout_act",
     "ms_env_rollout_act_free", "ms_env_rollout_act_free_supported", "ms_env_rollout_fill_common", "ms_env_round", "ms_env_flags", "ms_env_randbelow", "ms_env_auctioneer",
     "ms_env_get_rng", "ms_env_set_rng", "ms_env_export",
-    "ms_env_import", "ms_policy_act", "ms_policy_act_common", "ms_policy_act_compact",
+    "ms_env_import", "ms_env_snapshot", "ms_env_restore", "ms_policy_act", "ms_policy_act_common", "ms_policy_act_compact",
     "ms_act_round_free", "ms_policy_act_greedy", "ms_act_round_greedy", "ms_price_table_build", "ms_act_frag_bytes", "ms_act_prepare", "ms_offer_act_free", "ms_discounted_returns", "ms_unit_returns",
     "ms_ppo_workspace_bytes", "ms_ppo_grad", "ms_adam_step", "ms_adam_step_dev",
     "ms_aggregate_obs", "ms_decode_aggregated", "ms_dqn_act", "ms_dqn_workspace_bytes", "ms_dqn_grad",

@@ -18,6 +18,7 @@
 #include "ms_bdqn.h"
 #include "ms_wide.h"
 #include "ms_ppo.h"
+#include "ms_snapshot.h"
 
 namespace ms {
 hipError_t launch_bdqn_update(const BdqnUpd&, hipStream_t);
@@ -76,6 +77,9 @@ hipError_t launch_bdqn_l1_compact(const BdqnL1Compact&, hipStream_t);
 hipError_t launch_bdqn_act(const BdqnAct&, hipStream_t);
 hipError_t launch_wide_act(const WideAct&, hipStream_t);
 hipError_t launch_wide_grad(const WideRows&, const WideGrads&, const WideReduce&, hipStream_t);
+hipError_t launch_snap_pack(const Params&, const SnapArgs&, const SnapHeader&, const uint8_t*, uint64_t*, hipStream_t);
+hipError_t launch_snap_unpack(const Params&, const SnapArgs&, hipStream_t);
+hipError_t launch_snap_validate(const Params&, const SnapArgs&, unsigned long long*, hipStream_t);
 }  // namespace ms
 
 // work split of k_ppo_grad: ~kGradWaves wave chunks over all groups (4 per block), >= 8 tiles of 16 rows each
@@ -683,6 +687,98 @@ int ms_env_import(ms_env* env, const ms_state_host* in, void* stream) {
     *env->err_host = 0;
     for (int64_t e = 0; e < env->E; e++)
         if (in->flags && (in->flags[e] & MS_FATAL_FLAGS)) *env->err_host = 1;
+    return MS_OK;
+}
+
+// the env's configuration as the snapshot header stores it: the struct's bytes with its padding zeroed
+static void snap_config_bytes(const ms_config& c, uint8_t* out) {
+    memcpy(out, &c, sizeof(ms_config));
+    const size_t a = offsetof(ms_config, commercial_reward) + sizeof(int32_t), b = offsetof(ms_config, net_zero_offer_reward);
+    memset(out + a, 0, b - a);
+}
+
+int ms_env_snapshot(ms_env* env, void* dev_buf, size_t cap_bytes, size_t* used_bytes, void* stream) {
+    if (!env || !used_bytes) return fail(MS_EINVAL, "env/used_bytes is NULL");
+    if (dev_buf && ((uintptr_t)dev_buf & 15)) return fail(MS_EINVAL, "the snapshot buffer must be 16-byte aligned");
+    const ms::Params& P = env->P;
+    hipStream_t st = (hipStream_t)stream;
+    // Everything before the entries depends on the shape only. With a buffer that holds at least that much, the
+    // counts, the offsets, the header and the copies are queued at once and the host waits once: a replica's
+    // entries are written only where the capacity holds them, and a buffer that proves too small is refused
+    // after the wait. A smaller buffer, or none, only counts.
+    const ms::SnapLayout fixed = ms::snap_layout(env->E, P.rec_bytes, 0);
+    const bool room = dev_buf && cap_bytes >= fixed.o_liab;
+    ms::SnapArgs a{env->recs, env->mt, env->liab, room ? (uint8_t*)dev_buf : nullptr, cap_bytes, fixed, env->E, 0};
+    ms::SnapHeader h{};
+    h.magic = ms::kSnapMagic;
+    h.version = ms::kSnapVersion;
+    h.E = env->E;
+    h.N = P.N, h.C = P.C, h.L = P.L, h.cap = P.cap, h.rec_bytes = P.rec_bytes;
+    h.cfg_bytes = (int32_t)sizeof(ms_config);
+    uint8_t cfg_bytes[sizeof(ms_config)];
+    snap_config_bytes(env->cfg, cfg_bytes);
+    // the count comes back through the env's host-coherent words (behind the sticky error word)
+    volatile uint64_t* total = (volatile uint64_t*)(env->err_host + 2);
+    HIP_TRY(ms::launch_snap_pack(P, a, h, cfg_bytes, (uint64_t*)total, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const ms::SnapLayout lay = ms::snap_layout(env->E, P.rec_bytes, (int64_t)*total);
+    *used_bytes = (size_t)lay.total;
+    if (dev_buf && cap_bytes < lay.total)
+        return fail(MS_EINVAL, "snapshot buffer of %zu bytes is too small: %llu needed", cap_bytes,
+                    (unsigned long long)lay.total);
+    return MS_OK;
+}
+
+int ms_env_restore(ms_env* env, const void* dev_buf, size_t bytes, void* stream) {
+    if (!env || !dev_buf) return fail(MS_EINVAL, "env/snapshot is NULL");
+    if ((uintptr_t)dev_buf & 15) return fail(MS_EINVAL, "the snapshot buffer must be 16-byte aligned");
+    const ms::Params& P = env->P;
+    hipStream_t st = (hipStream_t)stream;
+    const uint8_t* buf = (const uint8_t*)dev_buf;
+    const ms::SnapLayout fixed = ms::snap_layout(env->E, P.rec_bytes, 0);
+    if (bytes < sizeof(ms::SnapHeader)) return fail(MS_EINVAL, "snapshot of %zu bytes is shorter than its header", bytes);
+    HIP_TRY(hipStreamSynchronize(st));
+    ms::SnapHeader h;
+    HIP_TRY(hipMemcpy(&h, buf, sizeof(h), hipMemcpyDeviceToHost));
+    if (h.magic != ms::kSnapMagic) return fail(MS_EINVAL, "not an env snapshot (magic %08x)", h.magic);
+    if (h.version != ms::kSnapVersion)
+        return fail(MS_EINVAL, "snapshot layout version %u, this library reads %u", h.version, ms::kSnapVersion);
+    if (h.N != P.N || h.C != P.C || h.L != P.L || h.cap != P.cap || h.rec_bytes != P.rec_bytes ||
+        h.cfg_bytes != (int32_t)sizeof(ms_config))
+        return fail(MS_EINVAL, "snapshot of shape %d x %d x %d (cap %d, %d-byte records), the env is %d x %d x %d (cap %d, %d)",
+                    h.N, h.C, h.L, h.cap, h.rec_bytes, P.N, P.C, P.L, P.cap, P.rec_bytes);
+    if (h.E != env->E) return fail(MS_EINVAL, "snapshot of %lld replicas, the env has %lld", (long long)h.E, (long long)env->E);
+    if (h.n_liab < 0 || (uint64_t)h.n_liab > (uint64_t)env->E * P.C * P.cap)
+        return fail(MS_EINVAL, "snapshot header: n_liab %lld out of range", (long long)h.n_liab);
+    const ms::SnapLayout lay = ms::snap_layout(env->E, P.rec_bytes, h.n_liab);
+    if (h.total_bytes != lay.total || bytes != lay.total)
+        return fail(MS_EINVAL, "snapshot of %zu bytes (header: %llu), its sections take %llu", bytes,
+                    (unsigned long long)h.total_bytes, (unsigned long long)lay.total);
+    uint8_t want[sizeof(ms_config)], got[sizeof(ms_config)];
+    snap_config_bytes(env->cfg, want);
+    HIP_TRY(hipMemcpy(got, buf + fixed.o_cfg, sizeof(got), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < sizeof(got); i++)
+        if (got[i] != want[i]) return fail(MS_EINVAL, "snapshot of another configuration (ms_config byte %zu differs)", i);
+    // [0] the first failing (replica, failure), [1] the OR of the records' flags
+    unsigned long long* res_dev = (unsigned long long*)env->scratch_u32;
+    unsigned long long res[2];
+    HIP_TRY(hipMemsetAsync(res_dev, 0xff, 8, st));
+    HIP_TRY(hipMemsetAsync(res_dev + 1, 0, 8, st));
+    ms::SnapArgs a{env->recs, env->mt, env->liab, const_cast<uint8_t*>(buf), lay.total, lay, env->E, h.n_liab};
+    HIP_TRY(ms::launch_snap_validate(P, a, res_dev, st));
+    HIP_TRY(hipMemcpyAsync(res, res_dev, sizeof(res), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (res[0] != ~0ull) {
+        const uint32_t f = (uint32_t)(res[0] & 0xffffffu);
+        return fail(MS_EINVAL, "snapshot env %lld: %s (index %d)", (long long)(res[0] >> 24),
+                    ms::snap_code_name(ms::snap_fail_code(f)), ms::snap_fail_index(f));
+    }
+    HIP_TRY(ms::launch_snap_unpack(P, a, st));
+    int32_t round0 = 0;
+    HIP_TRY(hipMemcpyAsync(&round0, buf + lay.o_recs, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    env->round = round0;
+    *env->err_host = ((uint32_t)res[1] & MS_FATAL_FLAGS) ? 1 : 0;
     return MS_OK;
 }
 

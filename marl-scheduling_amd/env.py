@@ -366,6 +366,55 @@ class BatchedEnv:
                 v[...] = np.asarray(state[k]).reshape(v.shape).astype(v.dtype)
         check(lib.ms_env_import(self._h, ct.byref(self._struct(arrs)), stream_ptr(stream)))
 
+    # ---- packed snapshot (ms_env_snapshot / ms_env_restore, ABI 22): the state for checkpoints
+    def snapshot_bytes(self, n_liab: int) -> int:
+        """Size of a snapshot holding n_liab live liability entries (the formula of marlsched.h)."""
+        a16 = lambda x: (x + 15) & ~15
+        return (a16(64 + ct.sizeof(abi.MsConfig)) + self.E * (self.shape.env_record_bytes + 4 * 624) +
+                a16(8 * (self.E + 1)) + a16(8 * int(n_liab)))
+
+    def snapshot(self, out: torch.Tensor | None = None, stream=None) -> torch.Tensor:
+        """The env's whole state packed into one uint8 device tensor of the exact size (records, the current
+        MT19937 block and the live liability entries of every replica; the layout is in marlsched.h). out: a
+        uint8 device tensor to pack into; its leading bytes are returned as a view (MarlSchedError 22 when it
+        is too small). Synchronous."""
+        if not has("ms_env_snapshot"):
+            raise RuntimeError("the loaded libmarlsched.so has no ms_env_snapshot (ABI < 22)")
+        used = ct.c_size_t()
+        if out is None:
+            # The size depends on the number of live entries. The first snapshot asks for it (a counting call);
+            # later ones allocate for the last count plus an eighth and pack at once, asking again only when
+            # the chains grew past that. The result is the exact-size view of that allocation.
+            last = getattr(self, "_snapshot_entries", None)
+            if last is None:
+                check(lib.ms_env_snapshot(self._h, None, 0, ct.byref(used), stream_ptr(stream)))
+                room = int(used.value)
+            else:
+                room = self.snapshot_bytes(last + last // 8 + 1024)
+            out = torch.empty(room, dtype=torch.uint8, device=self.device)
+            rc = lib.ms_env_snapshot(self._h, ptr(out), room, ct.byref(used), stream_ptr(stream))
+            if rc == abi.EINVAL and int(used.value) > room:
+                room = int(used.value)
+                out = torch.empty(room, dtype=torch.uint8, device=self.device)
+                rc = lib.ms_env_snapshot(self._h, ptr(out), room, ct.byref(used), stream_ptr(stream))
+            check(rc)
+            self._snapshot_entries = (int(used.value) - self.snapshot_bytes(0)) // 8
+            return out[: int(used.value)]
+        assert out.dtype == torch.uint8 and out.is_contiguous() and out.device == self.device
+        check(lib.ms_env_snapshot(self._h, ptr(out), out.numel(), ct.byref(used), stream_ptr(stream)))
+        return out[: int(used.value)]
+
+    def restore(self, snap: torch.Tensor, stream=None):
+        """Replace the env's state with a snapshot (a uint8 tensor, device or CPU) after the library validated
+        it against this env; a refused snapshot (MarlSchedError 22) leaves the env exactly as it was."""
+        if not has("ms_env_restore"):
+            raise RuntimeError("the loaded libmarlsched.so has no ms_env_restore (ABI < 22)")
+        assert snap.dtype == torch.uint8 and snap.dim() == 1
+        dev = snap.to(self.device).contiguous()
+        if dev.data_ptr() % 16:  # (a view into a larger tensor)
+            dev = dev.clone()
+        check(lib.ms_env_restore(self._h, ptr(dev), dev.numel(), stream_ptr(stream)))
+
 
 def decode_accepted(raw: torch.Tensor) -> np.ndarray:
     """[E,C,16] int8 ms_accept_rec bytes -> numpy structured array."""

@@ -1079,6 +1079,28 @@ class Trainer:
             res["trace"] = rounds
         return res
 
+    # ---- checkpoints (checkpoint.py)
+    def save_checkpoint(self, path: str) -> dict:
+        """Everything a resumed run needs, in one file written atomically: nets, Adam state, counters, one packed
+        env snapshot per replica part and (with metrics) the episode accumulators and log. Legal between
+        iterations only (after iteration() or update()). Several ranks: a path per rank. Returns the save's
+        timing split."""
+        from . import checkpoint
+        return checkpoint.save(self, path)
+
+    def load_checkpoint(self, path: str) -> dict:
+        """Resume from save_checkpoint's file, bit for bit: the trainer must have been built with the same
+        arguments (ValueError naming the first differing manifest field; the trainer is left as it was). Works on
+        a new trainer and on one that has already run. Returns the manifest."""
+        from . import checkpoint
+        return checkpoint.load(self, path)
+
+    def load_policy(self, path: str) -> dict:
+        """The nets only (policy and policy_old) from a checkpoint of any E, T, seed or world size with this
+        trainer's shape terms, arch and price mode: evaluate() then runs the saved policy."""
+        from . import checkpoint
+        return checkpoint.load_policy(self, path)
+
     def args_dict(self, replica="mean", params=None):
         """argsDict of the finished episodes (trainPPO.py:229-243): replica = "mean" averages the
         replicas' values per episode, an int picks one replica."""
