@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define MS_ABI_VERSION 22
+#define MS_ABI_VERSION 23
 
 #define MS_MAX_KINDS 16
 #define MS_MAX_AGENTS 64
@@ -253,6 +253,28 @@ int ms_env_reset(ms_env* env, const ms_obs_out* obs, void* stream);
  * once an earlier completed round has raised a fatal flag (MS_FATAL_FLAGS). */
 int ms_env_step(ms_env* env, const ms_actions* act, const ms_obs_out* obs,
                 const ms_reward_out* rew, const ms_event_out* ev, void* stream);
+
+/* A mixed population (ABI 23, fixed prices only): the agents whose bit is set in hardcoded_agents play
+ * DividedHardcodedAgent.getActions (Agent.py:630-641) in-kernel, the others the rows of ms_actions, as when
+ * world.agents holds DividedHardcodedAgents at some indices and another agent class at the rest
+ * (SchedulingEnv.getActionForAllAgents, SchedulingEnvironment.py:150-172, asks the agents in index order).
+ * Draw order on each replica's env stream: the masked agents in ascending index; per agent its L offerers
+ * (HardcodedModules.py:81-109), then its acceptors of the cores it owns whose best offered ratio beats its
+ * own job's (:16-45), each a random.sample(candidates, 1); all before the auctioneer's draws and the spawn.
+ * An agent with its bit clear draws nothing. The supplied rows of a masked agent are ignored whatever they
+ * hold (no MS_FLAG_BAD_ACTION from them). */
+typedef struct ms_mixed {
+    uint64_t hardcoded_agents;   /* bit a: agent a (ownerID a + 1) plays DividedHardcodedAgent.getActions in-kernel */
+    int8_t* acceptor_taken;      /* [E][N][C] or NULL: the acceptor actions the round used, after the substitution */
+    int8_t* offer_core_taken;    /* [E][N][L] or NULL: the offer actions the round used */
+} ms_mixed;
+
+/* ms_env_step with a mixed population. act->acceptor and act->offer_core must both be given (also when every
+ * bit is set); act->auctioneer works as in ms_env_step. hardcoded_agents == 0 is ms_env_step exactly (the
+ * taken arrays then receive the supplied rows). MS_EINVAL, launching nothing: a free-price env, a bit at or
+ * above n_agents, mix == NULL, a missing action array. MS_EOVERFLOW as in ms_env_step. */
+int ms_env_step_mixed(ms_env* env, const ms_actions* act, const ms_mixed* mix, const ms_obs_out* obs,
+                      const ms_reward_out* rew, const ms_event_out* ev, void* stream);
 
 /* Host round counter (all replicas advance together). */
 int64_t ms_env_round(const ms_env* env);

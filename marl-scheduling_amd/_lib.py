@@ -27,7 +27,7 @@ class MarlSchedError(RuntimeError):
         self.code = code
 
 
-ABI_VERSION = 22  # include/marlsched.h MS_ABI_VERSION
+ABI_VERSION = 23  # include/marlsched.h MS_ABI_VERSION
 
 
 def _load():
@@ -49,6 +49,9 @@ def _load():
         "ms_env_reset": (ct.c_int, [P, ct.POINTER(abi.MsObsOut), P]),
         "ms_env_step": (ct.c_int, [P, ct.POINTER(abi.MsActions), ct.POINTER(abi.MsObsOut),
                                    ct.POINTER(abi.MsRewardOut), ct.POINTER(abi.MsEventOut), P]),
+        "ms_env_step_mixed": (ct.c_int, [P, ct.POINTER(abi.MsActions), ct.POINTER(abi.MsMixed),
+                                         ct.POINTER(abi.MsObsOut), ct.POINTER(abi.MsRewardOut),
+                                         ct.POINTER(abi.MsEventOut), P]),
         "ms_env_step_act": (ct.c_int, [P, ct.POINTER(abi.MsActions), ct.POINTER(abi.MsObsOut),
                                        ct.POINTER(abi.MsRewardOut), ct.POINTER(abi.MsEventOut),
                                        ct.POINTER(abi.MsFusedAct), P]),
@@ -137,9 +140,10 @@ def _load():
     # does not read: the trainer passes them from ABI 20 on only), 21 episode metrics inside ms_env_step_act /
     # ms_env_rollout_act / ms_env_rollout_act_free (an older library refuses them: the trainer then keeps the
     # launch-per-round path under metrics), 22 the packed env snapshot (ms_env_snapshot / ms_env_restore: an older
-    # library has no checkpoints). An older library (an A/B variant built before them,
+    # library has no checkpoints), 23 ms_env_step_mixed (an older library has no mixed populations: BatchedEnv.step_mixed
+    # raises). An older library (an A/B variant built before them,
     # tools/gpu_job.sh ab step) loads without them only when MARLSCHED_LENIENT_ABI=1 asks for it
-    lenient = os.environ.get("MARLSCHED_LENIENT_ABI") == "1" and version in (13, 14, 15, 16, 17, 18, 19, 20, 21, 22)
+    lenient = os.environ.get("MARLSCHED_LENIENT_ABI") == "1" and version in (13, 14, 15, 16, 17, 18, 19, 20, 21, 22, 23)
     if version != ABI_VERSION and not lenient:
         raise ImportError("libmarlsched.so ABI version mismatch (%d, want %d)" % (version, ABI_VERSION))
     for name, (res, args) in sig.items():
@@ -147,7 +151,8 @@ def _load():
                 or (version < 16 and (name.startswith("ms_env_step_act") or name == "ms_env_rollout_act")) \
                 or (version < 17 and name.startswith("ms_env_rollout_act_free")) \
                 or (version < 19 and name.endswith("_greedy")) \
-                or (version < 22 and name in ("ms_env_snapshot", "ms_env_restore")):
+                or (version < 22 and name in ("ms_env_snapshot", "ms_env_restore")) \
+                or (version < 23 and name == "ms_env_step_mixed"):
             continue
         if lenient and not hasattr(L, name):  # an older build of this ABI (A/B variants)
             continue
@@ -169,7 +174,7 @@ def has(name: str) -> bool:
 # every entry point include/marlsched.h declares (checked by tests)
 EXPORTED = (
     "ms_last_error", "ms_abi_version", "ms_config_shape", "ms_env_create", "ms_env_destroy", "ms_env_shape",
-    "ms_env_reset", "ms_env_step", "ms_env_step_act", "ms_env_step_act_supported", "ms_env_rollout_act",
+    "ms_env_reset", "ms_env_step", "ms_env_step_mixed", "ms_env_step_act", "ms_env_step_act_supported", "ms_env_rollout_act",
     "ms_env_rollout_act_free", "ms_env_rollout_act_free_supported", "ms_env_rollout_fill_common", "ms_env_round", "ms_env_flags", "ms_env_randbelow", "ms_env_auctioneer",
     "ms_env_get_rng", "ms_env_set_rng", "ms_env_export",
     "ms_env_import", "ms_env_snapshot", "ms_env_restore", "ms_policy_act", "ms_policy_act_common", "ms_policy_act_compact",

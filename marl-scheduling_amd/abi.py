@@ -80,6 +80,11 @@ class MsActions(ct.Structure):
     ]
 
 
+class MsMixed(ct.Structure):
+    _fields_ = [("hardcoded_agents", ct.c_uint64), ("acceptor_taken", ct.c_void_p),
+                ("offer_core_taken", ct.c_void_p)]
+
+
 class MsObsOut(ct.Structure):
     _fields_ = [("acceptor", ct.c_void_p), ("offer", ct.c_void_p), ("auctioneer", ct.c_void_p),
                 ("core_rows", ct.c_void_p), ("core_owner", ct.c_void_p)]

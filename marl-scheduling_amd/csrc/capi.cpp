@@ -25,7 +25,8 @@ hipError_t launch_bdqn_update(const BdqnUpd&, hipStream_t);
 hipError_t launch_env_init(const Params&, int64_t, uint8_t*, uint32_t*, Liab*, uint64_t, hipStream_t);
 hipError_t launch_env_reset(const Params&, int64_t, const uint8_t*, int8_t*, int8_t*, int8_t*, int8_t*, int8_t*,
                             hipStream_t);
-hipError_t launch_env_step(const Params&, int64_t, uint8_t*, uint32_t*, Liab*, const StepIO&, hipStream_t);
+hipError_t launch_env_step(const Params&, int64_t, uint8_t*, uint32_t*, Liab*, const StepIO&, const MixIO&,
+                           hipStream_t);
 hipError_t launch_env_step_act(const Params&, int64_t, uint8_t*, uint32_t*, Liab*, const StepIO&, const FusedAct&,
                                hipStream_t);
 bool env_step_act_supported(const Params&, int64_t);
@@ -265,7 +266,8 @@ struct RolloutArgs {
     int n_rounds, act_last;
 };
 static int env_step_impl(ms_env* env, const ms_actions* act, const ms_obs_out* obs, const ms_reward_out* rew,
-                         const ms_event_out* ev, const ms::FusedAct* fa, const RolloutArgs* ro, void* stream);
+                         const ms_event_out* ev, const ms::FusedAct* fa, const RolloutArgs* ro, void* stream,
+                         const ms::MixIO* mix = nullptr);
 static int fill_io(ms_env* env, const ms_actions* act, const ms_obs_out* obs, const ms_reward_out* rew,
                    const ms_event_out* ev, ms::StepIO* out);
 static int check_mlp(const ms_mlp_params* p, int32_t obs_stride, int32_t n_units, int32_t units_per_group);
@@ -273,6 +275,20 @@ static int check_mlp(const ms_mlp_params* p, int32_t obs_stride, int32_t n_units
 int ms_env_step(ms_env* env, const ms_actions* act, const ms_obs_out* obs, const ms_reward_out* rew,
                 const ms_event_out* ev, void* stream) {
     return env_step_impl(env, act, obs, rew, ev, nullptr, nullptr, stream);
+}
+
+int ms_env_step_mixed(ms_env* env, const ms_actions* act, const ms_mixed* mix, const ms_obs_out* obs,
+                      const ms_reward_out* rew, const ms_event_out* ev, void* stream) {
+    if (!env || !act || !mix) return fail(MS_EINVAL, "ms_env_step_mixed: env/actions/mix is NULL");
+    if (env->cfg.free_prices)
+        return fail(MS_EINVAL, "ms_env_step_mixed: the hard-coded agents are fixed-price only");
+    if (!act->acceptor || !act->offer_core)
+        return fail(MS_EINVAL, "ms_env_step_mixed: acceptor and offer_core actions must both be given");
+    const int N = env->P.N;
+    if (N < MS_MAX_AGENTS && (mix->hardcoded_agents >> N) != 0)
+        return fail(MS_EINVAL, "ms_env_step_mixed: hardcoded_agents has a bit at or above n_agents (%d)", N);
+    const ms::MixIO mx{mix->hardcoded_agents, mix->acceptor_taken, mix->offer_core_taken};
+    return env_step_impl(env, act, obs, rew, ev, nullptr, nullptr, stream, &mx);
 }
 
 // the checks ms_env_step_act and ms_env_rollout_act share; fills fa
@@ -336,7 +352,8 @@ int ms_env_step_act_supported(const ms_env* env) {
 }
 
 static int env_step_impl(ms_env* env, const ms_actions* act, const ms_obs_out* obs, const ms_reward_out* rew,
-                         const ms_event_out* ev, const ms::FusedAct* fa, const RolloutArgs* ro, void* stream) {
+                         const ms_event_out* ev, const ms::FusedAct* fa, const RolloutArgs* ro, void* stream,
+                         const ms::MixIO* mix) {
     if (!env || !act) return fail(MS_EINVAL, "env/actions is NULL");
     if (!act->acceptor != !act->offer_core)
         return fail(MS_EINVAL, "acceptor and offer_core actions are given together (both NULL: hard-coded agents)");
@@ -356,7 +373,8 @@ static int env_step_impl(ms_env* env, const ms_actions* act, const ms_obs_out* o
     else if (fa)
         HIP_TRY(ms::launch_env_step_act(env->P, env->E, env->recs, env->mt, env->liab, io, *fa, (hipStream_t)stream));
     else
-        HIP_TRY(ms::launch_env_step(env->P, env->E, env->recs, env->mt, env->liab, io, (hipStream_t)stream));
+        HIP_TRY(ms::launch_env_step(env->P, env->E, env->recs, env->mt, env->liab, io, mix ? *mix : ms::MixIO{},
+                                    (hipStream_t)stream));
     env->round += ro ? ro->n_rounds : 1;
     return MS_OK;
 }

@@ -825,9 +825,12 @@ __device__ void hardcoded_auctioneer(Rec& R, const Geom& P, const M128* s_mc, co
 // and the best offered ratio beats its own job's; random.sample over the tied maxima), all on the
 // env stream before the auctioneer draws. The offer rows of all slots hold the same core pairs, so
 // one candidate mask serves every offerer. Writes the staged action arrays (LDS). Needs LPE >= C.
+// hc_mask (ms_env_step_mixed): bit a set = agent a plays the rules; the others keep their staged
+// rows and draw nothing, as when world.agents holds another agent class at their index
+// (SchedulingEnvironment.py:150-172 asks the agents in index order).
 template <int LPE>
 __device__ void hardcoded_agents(Rec& R, const Geom& P, const M128* s_mc, const M128* s_mr, MtStream<LPE>& rs,
-                                 int8_t* a_acc, int8_t* a_off, const Lanes<LPE>& L) {
+                                 int8_t* a_acc, int8_t* a_off, const Lanes<LPE>& L, uint64_t hc_mask) {
     const int C = P.C, N = P.N, NL = P.NL, O = P.O, gl = L.gl;
     const int8_t* c_owner = R.core_owner();
     const int8_t* c_kind = R.core_kind();
@@ -898,10 +901,13 @@ __device__ void hardcoded_agents(Rec& R, const Geom& P, const M128* s_mc, const 
         }
         if (!(bn * od > on * bd)) nt = 0;  // max(listOfOfferdRatios) > ownRewardRatio
     }
-    for (int i = gl; i < N * C; i += LPE) a_acc[i] = (int8_t)O;
+    if (gl < C)
+        for (int a = 0; a < N; a++)
+            if ((hc_mask >> a) & 1ull) a_acc[a * C + gl] = (int8_t)O;
     wave_sync();
     // the draws, in getActions order
     for (int a = 0; a < N; a++) {
+        if (!((hc_mask >> a) & 1ull)) continue;
         for (int j = 0; j < P.L; j++) {
             const uint32_t pick = rs.randbelow(nc, L);
             uint64_t m = cand;
@@ -1023,7 +1029,8 @@ constexpr int kLiabPrefetch = 4;  // newest chain entries loaded ahead per core 
 
 // One round of SchedulingEnv.step (SchedulingEnvironment.py:32-83): group g of block b steps env
 // b * (64 / LPE) + g. Each group owns a P.s_total-byte slice of the block's LDS. EXT: the kernel
-// variant with the optional features (hard-coded agents when io.act_acc == NULL, episode metrics,
+// variant with the optional features (hard-coded agents when io.act_acc == NULL or for the agents of mix's mask,
+// the taken actions, episode metrics,
 // compact acceptor observations); the plain training round is compiled without them, so it carries
 // none of their registers (the compact emission beside the full rows costs ~90 spilled SGPRs). CMP:
 // the plain round that emits the compact acceptor observations instead of the [N][C] rows (the
@@ -1034,10 +1041,11 @@ constexpr int kLiabPrefetch = 4;  // newest chain entries loaded ahead per core 
 template <int LPE, bool EXT, bool CMP, class SH, bool MET = EXT, bool SEQ = false>
 __device__ __forceinline__ void env_round(const Params& P, int64_t E, uint8_t* recs, uint32_t* mt, Liab* liab,
                                           const StepIO& io, int64_t slot, int lane_arg = -1,
-                                          uint8_t* wave_lds = nullptr, const int8_t* acc_lds = nullptr) {
+                                          uint8_t* wave_lds = nullptr, const int8_t* acc_lds = nullptr,
+                                          const MixIO* mix = nullptr) {
     // wave_lds: the wave's part of a multi-wave workgroup's LDS (k_env_rollout_act_free), else the block's;
     // acc_lds: the acceptor actions of the wave's replicas in the LDS ([kWave / LPE][N * C]; read instead of
-    // io.act_acc, which then serves the padding replicas only)
+    // io.act_acc, which then serves the padding replicas only); mix: k_env_step's mixed population (EXT only)
     extern __shared__ __align__(16) uint8_t smem_dyn[];
     uint8_t* const smem_all = wave_lds ? wave_lds : smem_dyn;
     // the shape: a compile-time constant for the BASELINE shapes (offsets fold into immediates,
@@ -1167,7 +1175,8 @@ __device__ __forceinline__ void env_round(const Params& P, int64_t E, uint8_t* r
     int8_t* o_price = R.offer_price();
     Liab* my_liab = liab + e * (int64_t)C * P.cap;
     // this round's episode accumulators (trainPPO.py:172-187): slot of episode round / episodeLength
-    const bool HC = EXT && io.act_acc == nullptr;
+    uint64_t hc_mask = 0;  // the agents that play the rules: all without supplied actions, else mix's
+    if constexpr (EXT) hc_mask = io.act_acc == nullptr ? ~0ull : (mix ? mix->hc_mask : 0ull);
     constexpr bool MX = MET;
     ms_env_metrics* mx = (MX && io.metrics && active)
                              ? io.metrics + (int64_t)((round / P.ep_len) % io.metrics_slots) * E + e
@@ -1199,9 +1208,18 @@ __device__ __forceinline__ void env_round(const Params& P, int64_t E, uint8_t* r
     MS_MARK(2);
     // ---- auctioneer actions: HardcodedAuctioneerAcceptor (HardcodedModules.py:54-78), asked by the
     //      driver before env.step (trainPPO.py:162); ties broken with random.sample -> _randbelow
-    if (HC) {  // HardcodedFixPriceEnvironment: the agents' actions come from the kernel
-        hardcoded_agents<LPE>(R, g, s_mc, s_mr, rs, a_acc, a_off, Lg);
+    if (hc_mask) {  // HardcodedFixPriceEnvironment: the agents' actions come from the kernel
+        hardcoded_agents<LPE>(R, g, s_mc, s_mr, rs, a_acc, a_off, Lg, hc_mask);
         wave_sync();
+    }
+    if constexpr (EXT) {
+        // the action arrays the round uses, after the substitution (ms_mixed)
+        if (mix && active) {
+            if (mix->acc_taken)
+                for (int i = gl; i < N * C; i += LPE) mix->acc_taken[e * N * C + i] = a_acc[i];
+            if (mix->off_taken)
+                for (int i = gl; i < NL; i += LPE) mix->off_taken[e * NL + i] = a_off[i];
+        }
     }
     if (!io.act_auct) {
         hardcoded_auctioneer<LPE>(R, g, s_mc, s_mr, rs, s_auct, Lg);
@@ -1852,7 +1870,7 @@ __device__ __forceinline__ void fused_act(const Params& P, int64_t E, const Fuse
 // compiler then keeps the whole round's state live across iterations: 3x the VGPRs.)
 template <int LPE, bool EXT, bool CMP, class SH>
 __global__ void __launch_bounds__(64, 4) k_env_step(Params P, int64_t E, uint8_t* recs, uint32_t* mt, Liab* liab,
-                                                 StepIO io) {
+                                                 StepIO io, MixIO mix) {
 #ifdef MS_PHASE_TIMING
     const uint64_t rt_start = __builtin_amdgcn_s_memrealtime();
 #endif
@@ -1863,7 +1881,7 @@ __global__ void __launch_bounds__(64, 4) k_env_step(Params P, int64_t E, uint8_t
         io.span[4 * blockIdx.x] = __builtin_amdgcn_s_memrealtime();
         io.span[4 * blockIdx.x + 2] = __builtin_amdgcn_s_memtime();
     }
-    env_round<LPE, EXT, CMP, SH>(P, E, recs, mt, liab, io, blockIdx.x);
+    env_round<LPE, EXT, CMP, SH>(P, E, recs, mt, liab, io, blockIdx.x, -1, nullptr, nullptr, EXT ? &mix : nullptr);
     if (io.span && threadIdx.x == 0) {
         io.span[4 * blockIdx.x + 3] = __builtin_amdgcn_s_memtime();
         io.span[4 * blockIdx.x + 1] = __builtin_amdgcn_s_memrealtime();
@@ -2915,15 +2933,17 @@ static int lanes_per_env(const Params& P, int64_t E) {
 
 template <int LPE, class SH>
 static hipError_t launch_step_sh(const Params& P, int64_t E, uint8_t* recs, uint32_t* mt, Liab* liab, const StepIO& io,
-                                 hipStream_t s) {
+                                 const MixIO& mix, hipStream_t s) {
     constexpr int G = kWave / LPE;
     const int64_t blocks = (E + G - 1) / G;
     const size_t lds = (size_t)P.s_total * G > 4 * kMtN ? (size_t)P.s_total * G : 4 * kMtN;  // >= one MT block
     const bool compact = io.obs_crow != nullptr || io.obs_cown != nullptr;
-    const bool ext = io.act_acc == nullptr || io.metrics != nullptr || (compact && io.obs_acc != nullptr);
+    // a mixed round (a mask, or the taken actions asked for) runs in the kernel of the optional features
+    const bool mixed = mix.hc_mask != 0 || mix.acc_taken != nullptr || mix.off_taken != nullptr;
+    const bool ext = io.act_acc == nullptr || io.metrics != nullptr || (compact && io.obs_acc != nullptr) || mixed;
     auto kern = ext ? k_env_step<LPE, true, false, DynShape>
                     : (compact ? k_env_step<LPE, false, true, SH> : k_env_step<LPE, false, false, SH>);
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(kWave), lds, s, P, E, recs, mt, liab, io);
+    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(kWave), lds, s, P, E, recs, mt, liab, io, mix);
     return hipGetLastError();
 }
 
@@ -2936,29 +2956,31 @@ static bool is_shape(const Params& P) {
 // round) run the kernel compiled for their geometry; every other shape the generic one.
 template <int LPE>
 static hipError_t launch_step_t(const Params& P, int64_t E, uint8_t* recs, uint32_t* mt, Liab* liab, const StepIO& io,
-                                hipStream_t s) {
+                                const MixIO& mix, hipStream_t s) {
 #ifndef MS_NO_FIXED_SHAPES
     if constexpr (LPE == 16) {
-        if (is_shape<8, 8, 3, 1>(P)) return launch_step_sh<LPE, FixShape<8, 8, 3, 1>>(P, E, recs, mt, liab, io, s);
-        if (is_shape<16, 16, 3, 1>(P)) return launch_step_sh<LPE, FixShape<16, 16, 3, 1>>(P, E, recs, mt, liab, io, s);
+        if (is_shape<8, 8, 3, 1>(P)) return launch_step_sh<LPE, FixShape<8, 8, 3, 1>>(P, E, recs, mt, liab, io, mix, s);
+        if (is_shape<16, 16, 3, 1>(P))
+            return launch_step_sh<LPE, FixShape<16, 16, 3, 1>>(P, E, recs, mt, liab, io, mix, s);
     }
     if constexpr (LPE == 32) {
-        if (is_shape<4, 4, 3, 1>(P)) return launch_step_sh<LPE, FixShape<4, 4, 3, 1>>(P, E, recs, mt, liab, io, s);
-        if (is_shape<32, 32, 3, 1>(P)) return launch_step_sh<LPE, FixShape<32, 32, 3, 1>>(P, E, recs, mt, liab, io, s);
+        if (is_shape<4, 4, 3, 1>(P)) return launch_step_sh<LPE, FixShape<4, 4, 3, 1>>(P, E, recs, mt, liab, io, mix, s);
+        if (is_shape<32, 32, 3, 1>(P))
+            return launch_step_sh<LPE, FixShape<32, 32, 3, 1>>(P, E, recs, mt, liab, io, mix, s);
     }
 #endif
-    return launch_step_sh<LPE, DynShape>(P, E, recs, mt, liab, io, s);
+    return launch_step_sh<LPE, DynShape>(P, E, recs, mt, liab, io, mix, s);
 }
 
 hipError_t launch_env_step(const Params& P, int64_t E, uint8_t* recs, uint32_t* mt, Liab* liab, const StepIO& io,
-                           hipStream_t s) {
+                           const MixIO& mix, hipStream_t s) {
     switch (lanes_per_env(P, E)) {
 #if MS_MIN_LPE <= 8
-        case 8: return launch_step_t<8>(P, E, recs, mt, liab, io, s);
+        case 8: return launch_step_t<8>(P, E, recs, mt, liab, io, mix, s);
 #endif
-        case 16: return launch_step_t<16>(P, E, recs, mt, liab, io, s);
-        case 32: return launch_step_t<32>(P, E, recs, mt, liab, io, s);
-        default: return launch_step_t<64>(P, E, recs, mt, liab, io, s);
+        case 16: return launch_step_t<16>(P, E, recs, mt, liab, io, mix, s);
+        case 32: return launch_step_t<32>(P, E, recs, mt, liab, io, mix, s);
+        default: return launch_step_t<64>(P, E, recs, mt, liab, io, mix, s);
     }
 }
 // ms_env_step_act: a wave's acceptor items one per lane (<= 64), its offer rows in 16-row tiles (<= 64) and

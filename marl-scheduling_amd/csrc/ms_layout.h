@@ -165,6 +165,14 @@ struct StepIO {
     int32_t metrics_slots;
 };
 
+// the mixed population of one ms_env_step_mixed call: an argument of k_env_step alone, so the fused
+// kernels' argument blocks (StepIO) stay as they are
+struct MixIO {
+    uint64_t hc_mask;    // bit a: agent a plays DividedHardcodedAgent.getActions in-kernel
+    int8_t* acc_taken;   // [E][N][C] or NULL: the acceptor actions the round used
+    int8_t* off_taken;   // [E][N][L] or NULL
+};
+
 // the fused next-round acting of ms_env_step_act (env_kernels.hip fused_act)
 struct FusedAct {
     ms_mlp_params off, acc;

@@ -184,6 +184,49 @@ class BatchedEnv:
                                   stream_ptr(stream)))
         return obs, rewards, events
 
+    def hardcoded_mask(self, hardcoded_agents) -> int:
+        """The ms_mixed.hardcoded_agents mask of an iterable of agent indices (0-based) or an int mask;
+        ValueError for an agent outside [0, N)."""
+        if isinstance(hardcoded_agents, (int, np.integer)) and not isinstance(hardcoded_agents, bool):
+            mask = int(hardcoded_agents)
+            if mask < 0 or mask >> self.N:
+                raise ValueError("hardcoded_agents mask 0x%x has a bit outside the %d agents" % (mask, self.N))
+            return mask
+        mask = 0
+        for a in hardcoded_agents:
+            if int(a) != a or not 0 <= int(a) < self.N:
+                raise ValueError("hardcoded agent %r is outside [0, %d)" % (a, self.N))
+            mask |= 1 << int(a)
+        return mask
+
+    def step_mixed(self, acceptor, offer_core, hardcoded_agents, auctioneer=None, obs=None, rewards=None,
+                   events=None, taken=None, stream=None):
+        """step() with a mixed population (ms_env_step_mixed, fixed prices): the agents in hardcoded_agents (an
+        iterable of 0-based indices, or an int mask with bit a for agent a) play DividedHardcodedAgent.getActions
+        (Agent.py:630-641) in the kernel, on the env stream before the auctioneer, in ascending index; the others
+        play their rows of acceptor [E,N,C] / offer_core [E,N,L], which must both be given (a masked agent's rows
+        are ignored whatever they hold). taken: an optional dict(acceptor=[E,N,C] int8, offer_core=[E,N,L] int8)
+        that receives the actions the round used. Returns (obs, rewards, events) like step."""
+        if self.free_prices:
+            raise ValueError("step_mixed: the hard-coded agents are fixed-price only")
+        if not has("ms_env_step_mixed"):
+            raise RuntimeError("the loaded libmarlsched.so has no ms_env_step_mixed (ABI < 23)")
+        mask = self.hardcoded_mask(hardcoded_agents)
+        taken = taken or {}
+        t_acc, t_off = taken.get("acceptor"), taken.get("offer_core")
+        for t, n in ((acceptor, self.N * self.C), (offer_core, self.N * self.L), (auctioneer, self.C),
+                     (t_acc, self.N * self.C), (t_off, self.N * self.L)):
+            if t is not None:
+                assert t.dtype == torch.int8 and t.is_contiguous() and t.device == self.device
+                assert t.numel() == self.E * n
+        obs = self.obs_buffers() if obs is None else obs
+        rewards = self.reward_buffers() if rewards is None else rewards
+        a, o, r, ev = self._step_structs(acceptor, offer_core, None, auctioneer, obs, rewards, events)
+        mix = abi.MsMixed(mask, ptr(t_acc), ptr(t_off))
+        check(lib.ms_env_step_mixed(self._h, ct.byref(a), ct.byref(mix), ct.byref(o), ct.byref(r),
+                                    ct.byref(ev) if ev else None, stream_ptr(stream)))
+        return obs, rewards, events
+
     @staticmethod
     def check_rings(rings, n_rounds: int):
         """The bounds contract of the one-launch rollouts (marlsched.h): each (tensor, stride, dtype) is a ring's

@@ -1019,7 +1019,7 @@ class Trainer:
 
     @torch.no_grad()
     def evaluate(self, episodes: int = 1, n_envs: int | None = None, mode: str = "greedy", seed: int | None = None,
-                 trace: bool = False) -> dict:
+                 trace: bool = False, hardcoded_agents=None) -> dict:
         """Evaluate the current policy (policy_old, the nets the next rollout acts with) for `episodes` episodes
         of episode_length rounds on n_envs (default: E) fresh replicas of their own; replica e is seeded
         seed + e (default seed: eval_seed()). Training state is left untouched: the training env, the rings,
@@ -1029,6 +1029,18 @@ class Trainer:
         mode "sample": the units sample as in training, Philox key from `seed`;
         mode "hardcoded": the in-kernel HardcodedOfferer / HardcodedAcceptor agents, the reference's baseline
         (fixed prices only: ValueError under free prices).
+
+        hardcoded_agents (an iterable of 0-based agent indices; modes "greedy" and "sample", fixed prices): a
+        mixed population. The given agents play the reference's DividedHardcodedAgent rules inside the env
+        kernel (BatchedEnv.step_mixed: on the env's stream, in ascending index, before the auctioneer) while the
+        others act with the nets; the act launch still runs for every unit and the kernel overrides the given
+        agents' rows. The result gains hardcoded_agents (the sorted indices) and, per entry of episodes,
+        agentRew_hardcoded / agentRew_learned: the mean of the episode's replica-averaged agentRew over the given
+        and over the other agents (None for an empty side). With trace, acceptor_action / offer_action are the
+        actions the round used (the rules' picks in the given agents' rows), so a trace replays on a restatement
+        or through step() once the rules' tie-break draws are made on the replaying env's stream.
+        ValueError with mode "hardcoded", under free prices and for an index outside [0, N). None (the default)
+        leaves the call and its result's keys as they are without the argument.
 
         Eager launches on the current stream (one act launch and one env round per round). Each call steps a
         newly created env (an env's reset re-emits observations; it does not rewind the world or its job
@@ -1045,6 +1057,16 @@ class Trainer:
         episodes, E = int(episodes), int(n_envs or self.E)
         if episodes < 1 or E < 1:
             raise ValueError("episodes and n_envs must be >= 1")
+        mixed = hardcoded_agents is not None
+        if mixed:
+            if mode == "hardcoded":
+                raise ValueError("hardcoded_agents selects agents of a learned population: mode 'greedy' or 'sample'")
+            if self.free:
+                raise ValueError("the hard-coded agents act under fixed prices only")
+            given = list(hardcoded_agents)
+            hc = sorted({int(a) for a in given})
+            if any(a != int(a) for a in given) or any(not 0 <= a < self.N for a in hc):
+                raise ValueError("hardcoded_agents must be agent indices in [0, %d)" % self.N)
         seed = self.eval_seed(E) if seed is None else int(seed)
         N, C, L = self.N, self.C, self.L
         b = self._eval_buffers(E)
@@ -1055,6 +1077,8 @@ class Trainer:
         mbuf = env.metrics_buffer(episodes)  # round r adds into slot (r // episode_length) % episodes
         philox_seed = (seed * 7919) & 0xFFFFFFFFFFFFFFFF
         rounds = []
+        if mixed:  # the actions the rounds used (the rules' picks in the given agents' rows)
+            taken = dict(acceptor=torch.empty_like(b["acc_action"]), offer_core=torch.empty_like(b["off_action"]))
         for t in range(episodes * self.ep_len):
             if mode == "hardcoded":
                 acts = (None, None, None)
@@ -1070,11 +1094,23 @@ class Trainer:
                         rec.update(price_state=b["price_state"].cpu(), price_action=b["price_action"].cpu(),
                                    offer_price=b["env_price"].cpu())
                 rounds.append(rec)
+            if mixed:
+                env.step_mixed(acts[0], acts[1], hc, obs=obs, rewards=b["rewards"], events=dict(metrics=mbuf),
+                               taken=taken)
+                if trace:
+                    rec.update(acceptor_action=taken["acceptor"].cpu(), offer_action=taken["offer_core"].cpu())
+                continue
             env.step(*acts, obs=obs, rewards=b["rewards"], events=dict(metrics=mbuf))
         raw = mbuf.cpu().numpy()
         per_replica = [mx.episode_values(mx.view(raw[k]), self.cfg, self.ep_len, N, C, L) for k in range(episodes)]
         res = dict(mode=mode, seed=seed, n_envs=E, episodes=[mx.reduce_replicas(ep) for ep in per_replica],
                    per_replica=per_replica)
+        if mixed:
+            res["hardcoded_agents"] = hc
+            rest = [a for a in range(N) if a not in hc]
+            for ep in res["episodes"]:
+                ep["agentRew_hardcoded"] = float(np.mean(ep["agentRew"][hc])) if hc else None
+                ep["agentRew_learned"] = float(np.mean(ep["agentRew"][rest])) if rest else None
         if trace:
             res["trace"] = rounds
         return res
