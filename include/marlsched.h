@@ -400,7 +400,9 @@ int ms_policy_act_compact(const ms_mlp_params* p, const int8_t* core_rows, const
  * (the offer price world.py:452 sees). uniforms: [2][E*U] (core, price) or NULL.
  * price_unit_stride: 0 = price_state / price_action / price_logprob in [E][U] rows; else >= E and
  * unit-major, row (e, u) at u * price_unit_stride + e (a rollout ring [U][T][E] with the round's
- * offset: the update reads one unit's rows of every replica contiguously). env_price stays [E][U]. */
+ * offset: the update reads one unit's rows of every replica contiguously). env_price stays [E][U].
+ * The two-net kernel is built for core choosers of up to 64 actions (C <= 63; the price chooser up to
+ * 127): MS_EINVAL beyond, nothing launched. */
 int ms_offer_act_free(const ms_mlp_params* core_chooser, const ms_mlp_params* price_chooser,
                       const int8_t* obs, int32_t obs_stride, int64_t n_envs, int32_t n_units,
                       int32_t units_per_group, int32_t n_cores, uint64_t seed, uint64_t offset,

@@ -988,6 +988,8 @@ int ms_offer_act_free(const ms_mlp_params* core, const ms_mlp_params* price, con
     if (price->in_dim != 4 || price->n_groups != core->n_groups) return fail(MS_EINVAL, "price chooser must be 4 -> A");
     if (core->in_dim != 2 * n_cores + 2 || core->n_actions != n_cores + 1)
         return fail(MS_EINVAL, "core chooser must be (2C+2) -> (C+1)");
+    if (core->n_actions > 64)  // dispatch_act: no two-net kernel with eight core-chooser tiles
+        return fail(MS_EINVAL, "the two-net act kernel is built for core choosers of up to 64 actions (n_cores <= 63)");
     if (n_envs < 1) return fail(MS_EINVAL, "n_envs must be >= 1");
     if (price_unit_stride != 0 && price_unit_stride < n_envs)
         return fail(MS_EINVAL, "price_unit_stride must be 0 or >= n_envs");

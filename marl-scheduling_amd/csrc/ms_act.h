@@ -146,7 +146,13 @@ struct W1Split {
 
 // The 16-wide layers and the head of one net, in registers: lane (j, g4) holds W2[j][4*g4 + s],
 // W3[16t + j][4*g4 + s] (the permuted-k A operands) and the biases of its accumulator rows.
-template <int NT>
+// ZFIX: the sampling never lands on an action whose numerator is exactly 0 (run2's second look, the tables'
+// zero entries: numerators()). The single launches and the table builders of policy_kernels.hip take it;
+// k_act_pair and the env round's fused acting keep the plain count (their code is the benchmark's, and the
+// check cost 1.3 to 3.3 % of a cfg3 step in either form tried: profiles/r14_act_buckets), so only the rows
+// they compute themselves, not the ones they sample from a table, can still meet the one-rounding-step
+// window described at run2.
+template <int NT, bool ZFIX = false>
 struct Head {
     float b1[4], w2[4], b2[4], w3[NT][4], b3[NT][4];  // b1, b2 pre-scaled by kTanhScale (fast_tanh_b)
     static constexpr int FW = 12 + 8 * NT;  // dwords of a lane's fragment
@@ -229,7 +235,8 @@ struct Head {
 
     // The softmax numerators of the tile's rows: z[t][q] = exp(logit - max) of action a = 16t + 4*g4 + q
     // of row j, S = the row's sum of z and c[t][q] = the running sum of z over actions 0..a (in increasing
-    // action order). The padding actions' -inf logits drop out of the max and the sums.
+    // action order; with ZFIX an action with a zero numerator: the running sum of the last nonzero action
+    // before it, 0 when there is none). The padding actions' -inf logits drop out of the max and the sums.
     __device__ __forceinline__ void numerators(f4 a1, int g4, float (&z)[NT][4], float (&c)[NT][4], float& S) const {
         float m = logits(a1, z);
         m = rows_max(m);
@@ -251,6 +258,7 @@ struct Head {
         //  rows_sum(lane_tot) bit for bit)
         if (NT > 1) S = rows_sum(lane_tot);
         float cum = 0.f;
+        [[maybe_unused]] float live_c = 0.f;  // ZFIX: the running sum of the last nonzero action so far (0: none)
 #pragma unroll
         for (int t = 0; t < NT; t++) {
             uint32_t gsr[4];
@@ -264,6 +272,32 @@ struct Head {
                 c[t][q] = cc;
             }
             cum += (gs0 + gs1) + (gs2 + gs3);
+            if constexpr (ZFIX) {
+                // A zero numerator takes the running sum of the last nonzero action before it, to the bit: the
+                // lanes and tiles add their sums in different orders, so its own sum can sit one rounding step
+                // above that one, and a u * S between the two would count up to the zero-probability action.
+                // With equal sums the count passes over it (or reaches the padding: last nonzero).
+                float mine_c = 0.f;  // the running sum of this lane's last nonzero action of the tile
+#pragma unroll
+                for (int q = 0; q < 4; q++) mine_c = z[t][q] > 0.f ? c[t][q] : mine_c;
+                uint32_t er[4];
+                rows_bcast(__float_as_uint(mine_c), er);
+                float prev = live_c;
+                if (g4 > 0 && gs0 > 0.f) prev = __uint_as_float(er[0]);
+                if (g4 > 1 && gs1 > 0.f) prev = __uint_as_float(er[1]);
+                if (g4 > 2 && gs2 > 0.f) prev = __uint_as_float(er[2]);
+#pragma unroll
+                for (int q = 0; q < 4; q++) {
+                    if (z[t][q] > 0.f)
+                        prev = c[t][q];
+                    else
+                        c[t][q] = prev;
+                }
+                if (gs0 > 0.f) live_c = __uint_as_float(er[0]);
+                if (gs1 > 0.f) live_c = __uint_as_float(er[1]);
+                if (gs2 > 0.f) live_c = __uint_as_float(er[2]);
+                if (gs3 > 0.f) live_c = __uint_as_float(er[3]);
+            }
         }
         if (NT == 1) S = cum;
     }
@@ -386,6 +420,31 @@ struct Head {
             for (int t = 0; t < NT; t++)
 #pragma unroll
                 for (int q = 0; q < 4; q++) mine[i] = (16 * t + 4 * g4 + q == cnt[i]) ? z[i][t][q] : mine[i];
+        if constexpr (ZFIX) {
+            // The count stopped on a zero numerator (this lane holds that action): the lanes and tiles add
+            // their running sums in different orders, so the sum of the last nonzero action can sit one
+            // rounding step below the next lane's, with u * S between the two. A zero-probability action is
+            // never drawn: the last action with nonzero probability before the count (the tables give their
+            // zero numerators that action's running sum: numerators()).
+            bool off[2];
+#pragma unroll
+            for (int i = 0; i < 2; i++) off[i] = ((cnt[i] >> 2) & 3) == g4 && mine[i] == 0.f;
+            if (__builtin_expect(__ballot(off[0] || off[1]) != 0, 0)) {
+#pragma unroll
+                for (int i = 0; i < 2; i++) {
+                    const int row_off = rows_max_i(off[i] ? 1 : 0);
+                    const int last_nz = last_nonzero_below(z[i], g4, cnt[i]);
+                    if (row_off && last_nz >= 0) cnt[i] = last_nz;
+                    mine[i] = 0.f;
+                }
+#pragma unroll
+                for (int i = 0; i < 2; i++)
+#pragma unroll
+                    for (int t = 0; t < NT; t++)
+#pragma unroll
+                        for (int q = 0; q < 4; q++) mine[i] = (16 * t + 4 * g4 + q == cnt[i]) ? z[i][t][q] : mine[i];
+            }
+        }
         rows_sum2(mine[0], mine[1]);
 #pragma unroll
         for (int i = 0; i < 2; i++) {
@@ -403,6 +462,16 @@ struct Head {
                 if (z[t][q] > 0.f) last_nz = 16 * t + 4 * g4 + q;
         last_nz = rows_max_i(last_nz);
         return last_nz;
+    }
+    // the row's last action below `below` with a nonzero numerator (-1: none), on every lane of the row
+    __device__ __forceinline__ static int last_nonzero_below(const float (&z)[NT][4], int g4, int below) {
+        int last_nz = -1;
+#pragma unroll
+        for (int t = 0; t < NT; t++)
+#pragma unroll
+            for (int q = 0; q < 4; q++)
+                if (z[t][q] > 0.f && 16 * t + 4 * g4 + q < below) last_nz = 16 * t + 4 * g4 + q;
+        return rows_max_i(last_nz);
     }
 
     __device__ __forceinline__ static float clamped_log(float pa) {
@@ -474,8 +543,8 @@ __device__ __forceinline__ const uint32_t* frag_groups(const ms_mlp_params& p, b
 
 // The common row's sampling table (Head::table) into LDS: its dwords (zero past the row: they meet
 // zero weights, like k_act's clamped loads) through layer 1 and the head. One wave.
-template <int S1, int NT>
-__device__ __forceinline__ void common_table(const W1Split<S1>& w1, const Head<NT>& h1, const int8_t* common,
+template <int S1, int NT, bool ZFIX>
+__device__ __forceinline__ void common_table(const W1Split<S1>& w1, const Head<NT, ZFIX>& h1, const int8_t* common,
                                              int stride4, uint32_t* tmpl, float* cum, float* lp, float* S, int* lnz,
                                              int lane) {
     const int j = lane & 15, g4 = lane >> 4;

@@ -87,7 +87,8 @@ struct PriceTW {
 // with the weights split in three bf16 terms (exact f32 weights; the int8 inputs are exact in bf16):
 // lane (j, g) loads dwords 8s + 2g, 8s + 2g + 1 of tile row j, which are exactly its B fragment of
 // k-step s. S1 = ceil(stride / 32) k-steps.
-template <int S1, int NT, int NT2, bool EXT_U>
+// (ZFIX: Head's; k_act's instantiations take it, k_act_pair's do not)
+template <int S1, int NT, int NT2, bool EXT_U, bool ZFIX = false>
 __device__ __forceinline__ void act_tiles(const ActArgs& a, int block) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int gw = block * 4 + __builtin_amdgcn_readfirstlane(tid >> 6);  // global wave index (wave-uniform)
@@ -125,7 +126,7 @@ __device__ __forceinline__ void act_tiles(const ActArgs& a, int block) {
         pdig = reinterpret_cast<int16_t*>(s_pd[wid]);
     }
     W1Split<S1> w1;
-    Head<NT> h1;
+    Head<NT, ZFIX> h1;
     if (const uint32_t* fg = frag_groups<S1, NT>(a.n1, false)) {  // made once per weight update
         using FL = FragLayout<S1, NT>;
         const uint32_t* lf = fg + (size_t)grp * FL::GB + lane * FL::LW;
@@ -353,7 +354,7 @@ __device__ __forceinline__ void act_tiles(const ActArgs& a, int block) {
         // the pairs the table could not serve (or every pair, without a table): the same pairs and
         // draws again, the core chooser recomputed (bit-identical), then the price net itself; its
         // weights take registers only here, after the main loop
-        Head<NP> h2;
+        Head<NP, ZFIX> h2;
         h2.load(a.n2, grp, j, g4);
         const float pw1 = a.n2.w1[((size_t)grp * 16 + j) * 4 + g4];  // W1p[j][g4] (K = 4 inputs)
         for (int tile = t0; tile < t1; tile += 2) {
@@ -397,7 +398,7 @@ __device__ __forceinline__ void act_tiles(const ActArgs& a, int block) {
 #endif
 constexpr int kCommonSeg = MS_COMMON_SEG;  // most rows per wave = capacity of the wave's LDS row list
 
-template <int S1, int NT, bool EXT_U, bool OWN>
+template <int S1, int NT, bool EXT_U, bool OWN, bool ZFIX = false>
 __device__ __forceinline__ void act_common_rows(const ActArgs& a, int block) {
     __shared__ int32_t s_list[4][kCommonSeg];
     __shared__ float s_ulist[4][kCommonSeg];  // the listed rows' uniforms (drawn in the scan)
@@ -414,7 +415,7 @@ __device__ __forceinline__ void act_common_rows(const ActArgs& a, int block) {
     const int A = a.n1.n_actions;
     const int stride4 = a.stride >> 2;
     W1Split<S1> w1;
-    Head<NT> h1;
+    Head<NT, ZFIX> h1;
     if (const uint32_t* fg = frag_groups<S1, NT>(a.n1, true)) {
         // the weights and the common row's sampling table as ms_act_prepare made them
         using FL = FragLayout<S1, NT>;

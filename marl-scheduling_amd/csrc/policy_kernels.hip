@@ -33,12 +33,12 @@ namespace ms {
 
 template <int S1, int NT, int NT2, bool EXT_U>
 __global__ void __launch_bounds__(256) k_act(ActArgs a) {
-    act_tiles<S1, NT, NT2, EXT_U>(a, blockIdx.x);
+    act_tiles<S1, NT, NT2, EXT_U, true>(a, blockIdx.x);
 }
 
 template <int S1, int NT, bool EXT_U, bool OWN>
 __global__ void __launch_bounds__(256) k_act_common(ActArgs a) {
-    act_common_rows<S1, NT, EXT_U, OWN>(a, blockIdx.x);
+    act_common_rows<S1, NT, EXT_U, OWN, true>(a, blockIdx.x);
 }
 
 template <int S1, int NT>
@@ -140,7 +140,7 @@ __global__ void __launch_bounds__(64) k_act_prep(ms_mlp_params p, const int8_t* 
     const int grp = blockIdx.x, lane = threadIdx.x, j = lane & 15, g4 = lane >> 4;
     W1Split<S1> w1;
     w1.load(p.w1 + (size_t)grp * 16 * p.in_dim, p.in_dim, j, g4);
-    Head<NT> h1;
+    Head<NT, true> h1;  // the tables' zero numerators: Head's ZFIX
     h1.load(p, grp, j, g4);
     uint32_t* gb = frag + 4 + (size_t)grp * FL::GB;
     w1.store_frag(gb + lane * FL::LW);
@@ -202,7 +202,7 @@ __global__ void __launch_bounds__(256) k_price_table(ms_mlp_params pn, const int
     const int tiles = (K + 15) / 16;
     const int grp = gw / tiles, tile = gw - grp * tiles;
     if (grp >= pn.n_groups) return;
-    Head<NT2> h;
+    Head<NT2, true> h;
     h.load(pn, grp, j, g4);
     const float pw1 = pn.w1[((size_t)grp * 16 + j) * 4 + g4];
     const int key = 16 * tile + j;
