@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define MS_ABI_VERSION 23
+#define MS_ABI_VERSION 24
 
 #define MS_MAX_KINDS 16
 #define MS_MAX_AGENTS 64
@@ -272,7 +272,10 @@ typedef struct ms_mixed {
 /* ms_env_step with a mixed population. act->acceptor and act->offer_core must both be given (also when every
  * bit is set); act->auctioneer works as in ms_env_step. hardcoded_agents == 0 is ms_env_step exactly (the
  * taken arrays then receive the supplied rows). MS_EINVAL, launching nothing: a free-price env, a bit at or
- * above n_agents, mix == NULL, a missing action array. MS_EOVERFLOW as in ms_env_step. */
+ * above n_agents, mix == NULL, a missing action array. MS_EOVERFLOW as in ms_env_step.
+ * Aliasing (ABI 24): acceptor_taken may be act->acceptor itself and offer_core_taken act->offer_core itself (the
+ * same pointers, not overlapping windows): a replica's supplied rows are all read before its taken rows are
+ * written, so the supplied arrays then end up holding the played trajectory. */
 int ms_env_step_mixed(ms_env* env, const ms_actions* act, const ms_mixed* mix, const ms_obs_out* obs,
                       const ms_reward_out* rew, const ms_event_out* ev, void* stream);
 
@@ -522,6 +525,24 @@ int ms_env_rollout_act(ms_env* env, const ms_actions* act, const ms_obs_out* obs
                        const ms_event_out* ev, const ms_fused_act* next, const ms_round_strides* strides,
                        int32_t n_rounds, int32_t act_after_last, void* stream);
 
+/* ABI 24: ms_env_step_act / ms_env_rollout_act with a mixed population (ms_mixed's rules, fixed prices only).
+ * hc_mask: bit a set = agent a plays DividedHardcodedAgent.getActions in every round of the call, on the replica's
+ * env stream in ascending agent index before the auctioneer, exactly as in ms_env_step_mixed; the one mask holds
+ * for every round and replica. Each round writes the actions it used for the masked agents back into that
+ * round's act->acceptor / act->offer_core rows (round t's arrays, advanced by the strides), so the arrays hold
+ * the played trajectory afterwards; the other agents' rows are not written. The fused acting still samples every
+ * unit of the next round; the masked agents' sampled actions are overridden by that round and their log-probs
+ * in `next` are left as sampled: they belong to no played action and must not be read.
+ * hc_mask == 0 runs the kernels of ms_env_step_act / ms_env_rollout_act. Outputs are bit-identical to
+ * ms_env_step_mixed rounds (taken = the action arrays) with an ms_act_round_free call between them.
+ * MS_EINVAL with a message, launching nothing: a free-price env, a bit at or above n_agents, a missing action
+ * array, and whatever ms_env_step_act / ms_env_rollout_act refuse. */
+int ms_env_step_act_mixed(ms_env* env, const ms_actions* act, const ms_obs_out* obs, const ms_reward_out* rew,
+                          const ms_event_out* ev, const ms_fused_act* next, uint64_t hc_mask, void* stream);
+int ms_env_rollout_act_mixed(ms_env* env, const ms_actions* act, const ms_obs_out* obs, const ms_reward_out* rew,
+                             const ms_event_out* ev, const ms_fused_act* next, const ms_round_strides* strides,
+                             int32_t n_rounds, int32_t act_after_last, uint64_t hc_mask, void* stream);
+
 /* ABI 17: the locally shared free-price rollout (BASELINE cfg3; LocallySharedPPO + FreePriceOfferPPO, DESIGN
  * §1) in one launch: every round's getActionForAllAgents (SchedulingEnvironment.py:150-172) fused after the env
  * round that built its observations. A workgroup steps 4 * N replicas (16 lanes each) and then acts for them
@@ -757,6 +778,13 @@ int ms_adam_step(const ms_adam_tensor* tensors, int32_t n_tensors, const double*
  * caller before each step): a captured HIP graph replays it with the current count. */
 int ms_adam_step_dev(const ms_adam_tensor* tensors, int32_t n_tensors, const double* lr, int32_t n_lr,
                      const int64_t* step_dev, double beta1, double beta2, double eps, void* stream);
+/* ABI 24: ms_adam_step_dev with frozen groups. Every tensor is [n_groups][numel / n_groups] (nets stacked over
+ * groups; numel must be a multiple of n_groups); frozen_dev (device, n_groups bytes, or NULL for none) marks the
+ * groups the step skips: their parameters, exp_avg and exp_avg_sq keep their bits whatever the gradient holds
+ * (NaN included), also with non-zero moments. The other groups step exactly as in ms_adam_step_dev. */
+int ms_adam_step_dev_masked(const ms_adam_tensor* tensors, int32_t n_tensors, const double* lr, int32_t n_lr,
+                            const int64_t* step_dev, double beta1, double beta2, double eps, int32_t n_groups,
+                            const uint8_t* frozen_dev, void* stream);
 
 /* ---- DQN units: DQNEntity (DQNmodules.py:34-94) and optimize_model (DQNmodules.py:97-154) for the
  * DQN env (DQNDividedFixedPricesEnv SchedulingEnvironment.py:351-436, DividedFixPriceDQNAgent

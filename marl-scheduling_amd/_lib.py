@@ -27,7 +27,7 @@ class MarlSchedError(RuntimeError):
         self.code = code
 
 
-ABI_VERSION = 23  # include/marlsched.h MS_ABI_VERSION
+ABI_VERSION = 24  # include/marlsched.h MS_ABI_VERSION
 
 
 def _load():
@@ -55,6 +55,13 @@ def _load():
         "ms_env_step_act": (ct.c_int, [P, ct.POINTER(abi.MsActions), ct.POINTER(abi.MsObsOut),
                                        ct.POINTER(abi.MsRewardOut), ct.POINTER(abi.MsEventOut),
                                        ct.POINTER(abi.MsFusedAct), P]),
+        "ms_env_step_act_mixed": (ct.c_int, [P, ct.POINTER(abi.MsActions), ct.POINTER(abi.MsObsOut),
+                                             ct.POINTER(abi.MsRewardOut), ct.POINTER(abi.MsEventOut),
+                                             ct.POINTER(abi.MsFusedAct), u64, P]),
+        "ms_env_rollout_act_mixed": (ct.c_int, [P, ct.POINTER(abi.MsActions), ct.POINTER(abi.MsObsOut),
+                                                ct.POINTER(abi.MsRewardOut), ct.POINTER(abi.MsEventOut),
+                                                ct.POINTER(abi.MsFusedAct), ct.POINTER(abi.MsRoundStrides), i32, i32,
+                                                u64, P]),
         "ms_env_step_act_supported": (ct.c_int, [P]),
         "ms_env_rollout_act": (ct.c_int, [P, ct.POINTER(abi.MsActions), ct.POINTER(abi.MsObsOut),
                                           ct.POINTER(abi.MsRewardOut), ct.POINTER(abi.MsEventOut),
@@ -105,6 +112,8 @@ def _load():
                                     ct.c_double, ct.c_double, P]),
         "ms_adam_step_dev": (ct.c_int, [ct.POINTER(abi.MsAdamTensor), i32, ct.POINTER(ct.c_double), i32, P,
                                         ct.c_double, ct.c_double, ct.c_double, P]),
+        "ms_adam_step_dev_masked": (ct.c_int, [ct.POINTER(abi.MsAdamTensor), i32, ct.POINTER(ct.c_double), i32, P,
+                                               ct.c_double, ct.c_double, ct.c_double, i32, P, P]),
         "ms_dqn_act": (ct.c_int, [ct.POINTER(abi.MsQnetParams), P, i32, i64, i32, i32, ct.c_double, P, u64, u64, P,
                                   P, P, P]),
         "ms_regen_agent_rows": (ct.c_int, [ct.POINTER(abi.MsConfig), P, P, P, P, P, i64, P, P, P]),
@@ -141,9 +150,11 @@ def _load():
     # ms_env_rollout_act / ms_env_rollout_act_free (an older library refuses them: the trainer then keeps the
     # launch-per-round path under metrics), 22 the packed env snapshot (ms_env_snapshot / ms_env_restore: an older
     # library has no checkpoints), 23 ms_env_step_mixed (an older library has no mixed populations: BatchedEnv.step_mixed
-    # raises). An older library (an A/B variant built before them,
+    # raises), 24 the mixed fused rollouts and the masked Adam step (ms_env_step_act_mixed, ms_env_rollout_act_mixed,
+    # ms_adam_step_dev_masked: without them a masked Trainer steps with a launch pair per round, and refuses frozen
+    # groups). An older library (an A/B variant built before them,
     # tools/gpu_job.sh ab step) loads without them only when MARLSCHED_LENIENT_ABI=1 asks for it
-    lenient = os.environ.get("MARLSCHED_LENIENT_ABI") == "1" and version in (13, 14, 15, 16, 17, 18, 19, 20, 21, 22, 23)
+    lenient = os.environ.get("MARLSCHED_LENIENT_ABI") == "1" and version in (13, 14, 15, 16, 17, 18, 19, 20, 21, 22, 23, 24)
     if version != ABI_VERSION and not lenient:
         raise ImportError("libmarlsched.so ABI version mismatch (%d, want %d)" % (version, ABI_VERSION))
     for name, (res, args) in sig.items():
@@ -152,7 +163,9 @@ def _load():
                 or (version < 17 and name.startswith("ms_env_rollout_act_free")) \
                 or (version < 19 and name.endswith("_greedy")) \
                 or (version < 22 and name in ("ms_env_snapshot", "ms_env_restore")) \
-                or (version < 23 and name == "ms_env_step_mixed"):
+                or (version < 23 and name == "ms_env_step_mixed") \
+                or (version < 24 and name in ("ms_env_step_act_mixed", "ms_env_rollout_act_mixed",
+                                              "ms_adam_step_dev_masked")):
             continue
         if lenient and not hasattr(L, name):  # an older build of this ABI (A/B variants)
             continue
@@ -175,6 +188,7 @@ def has(name: str) -> bool:
 EXPORTED = (
     "ms_last_error", "ms_abi_version", "ms_config_shape", "ms_env_create", "ms_env_destroy", "ms_env_shape",
     "ms_env_reset", "ms_env_step", "ms_env_step_mixed", "ms_env_step_act", "ms_env_step_act_supported", "ms_env_rollout_act",
+    "ms_env_step_act_mixed", "ms_env_rollout_act_mixed", "ms_adam_step_dev_masked",
     "ms_env_rollout_act_free", "ms_env_rollout_act_free_supported", "ms_env_rollout_fill_common", "ms_env_round", "ms_env_flags", "ms_env_randbelow", "ms_env_auctioneer",
     "ms_env_get_rng", "ms_env_set_rng", "ms_env_export",
     "ms_env_import", "ms_env_snapshot", "ms_env_restore", "ms_policy_act", "ms_policy_act_common", "ms_policy_act_compact",

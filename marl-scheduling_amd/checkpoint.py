@@ -91,8 +91,11 @@ def config_of(t: torch.Tensor) -> abi.MsConfig:
 
 def make_manifest(cfg: abi.MsConfig, arch: str, E: int, T: int, hyper, seed: int, rank: int = 0, world_size: int = 1,
                   parts: int = 1, free: bool = False, compact: bool = True, fused: bool = True,
-                  price_unit_major: bool = False, metrics: bool = False, ep_len: int = 1, metric_slots: int = 1) -> dict:
-    """What a trainer must be for a checkpoint's state to fit it (compare_manifest's order of fields)."""
+                  price_unit_major: bool = False, metrics: bool = False, ep_len: int = 1, metric_slots: int = 1,
+                  hardcoded_agents=None) -> dict:
+    """What a trainer must be for a checkpoint's state to fit it (compare_manifest's order of fields).
+    hardcoded_agents: the rule-based agents of a mixed market, a field only when there are some (a file without
+    the field, as every file written before the field existed, has none)."""
     m = dict(format=FORMAT_VERSION, config=config_tensor(cfg), arch=str(arch), E=int(E), T=int(T))
     for f in dataclasses.fields(hyper):
         v = getattr(hyper, f.name)
@@ -102,6 +105,8 @@ def make_manifest(cfg: abi.MsConfig, arch: str, E: int, T: int, hyper, seed: int
     m.update(seed=int(seed), rank=int(rank), world_size=int(world_size), parts=int(parts), free=bool(free),
              compact=bool(compact), fused=bool(fused), price_unit_major=bool(price_unit_major),
              metrics=bool(metrics), ep_len=int(ep_len), metric_slots=int(metric_slots))
+    if hardcoded_agents:
+        m["hardcoded_agents"] = sorted(int(a) for a in hardcoded_agents)
     return m
 
 
@@ -131,7 +136,7 @@ def compare_manifest(want: dict, got: dict, fields=None) -> None:
 def trainer_manifest(tr) -> dict:
     return make_manifest(tr.cfg, tr.arch, tr.E, tr.T, tr.hp, tr.seed, tr.rank, tr.world_size, len(tr.env.parts),
                          tr.free, tr.compact, tr.fused, bool(getattr(tr, "price_unit_major", False)),
-                         tr.metric_bufs is not None, tr.ep_len, tr.metric_slots)
+                         tr.metric_bufs is not None, tr.ep_len, tr.metric_slots, getattr(tr, "hardcoded", None))
 
 
 # ---- plain-data encoding of the episode log (numpy arrays are not weights_only data)
@@ -236,7 +241,11 @@ def load(tr, path: str) -> dict:
     trainer untouched), then every tensor is copied into the trainer's own in place, so a trainer that has
     already run (captured rollout and update graphs) resumes as well as a new one."""
     manifest, state = read_file(path)
-    compare_manifest(trainer_manifest(tr), manifest)
+    want = trainer_manifest(tr)
+    mine, theirs = want.get("hardcoded_agents") or [], manifest.get("hardcoded_agents") or []
+    if list(mine) != list(theirs):  # (an absent field: no rule-based agents)
+        raise ValueError("checkpoint does not fit: hardcoded_agents is %r, the trainer's is %r" % (theirs, mine))
+    compare_manifest(want, manifest)
     units = tr.units()
     if set(state["units"]) != {u.name for u in units} or len(state["env"]) != len(tr.env.parts):
         raise ValueError("checkpoint does not fit: unit types %s, %d env parts" % (sorted(state["units"]), len(state["env"])))

@@ -28,10 +28,10 @@ hipError_t launch_env_reset(const Params&, int64_t, const uint8_t*, int8_t*, int
 hipError_t launch_env_step(const Params&, int64_t, uint8_t*, uint32_t*, Liab*, const StepIO&, const MixIO&,
                            hipStream_t);
 hipError_t launch_env_step_act(const Params&, int64_t, uint8_t*, uint32_t*, Liab*, const StepIO&, const FusedAct&,
-                               hipStream_t);
+                               uint64_t, hipStream_t);
 bool env_step_act_supported(const Params&, int64_t);
 hipError_t launch_env_rollout_act(const Params&, int64_t, uint8_t*, uint32_t*, Liab*, const StepIO&, const FusedAct&,
-                                  const RoundStride&, int, int, hipStream_t);
+                                  const RoundStride&, int, int, uint64_t, hipStream_t);
 hipError_t launch_env_rollout_act_free(const Params&, int64_t, uint8_t*, uint32_t*, Liab*, const StepIO&,
                                        const FusedActFree&, const RoundStrideFree&, int, int, hipStream_t);
 bool env_rollout_free_supported(const Params&);
@@ -68,7 +68,7 @@ int ppo_partial_rows(int n_chunks, bool keyed);
 hipError_t launch_aggregate_obs(const AggArgs&, hipStream_t);
 hipError_t launch_decode_aggregated(const int32_t*, long long, int, int, int, int, int8_t*, int8_t*, int*, hipStream_t);
 hipError_t launch_adam(const AdamTensor*, int, const double*, int, int64_t, double, double, double, const int64_t*,
-                       hipStream_t);
+                       hipStream_t, const uint8_t* frozen = nullptr, int n_groups = 0);
 hipError_t launch_dqn_act(const DqnActArgs&, hipStream_t);
 hipError_t launch_regen_agent_rows(const RegenArgs&, hipStream_t);
 hipError_t launch_dqn_grad(const DqnGradArgs&, const DqnReduceArgs&, hipStream_t);
@@ -268,6 +268,7 @@ struct RolloutArgs {
 static int env_step_impl(ms_env* env, const ms_actions* act, const ms_obs_out* obs, const ms_reward_out* rew,
                          const ms_event_out* ev, const ms::FusedAct* fa, const RolloutArgs* ro, void* stream,
                          const ms::MixIO* mix = nullptr);
+static int fused_mixed_check(const ms_env* env, const ms_actions* act, uint64_t hc_mask, const char* who);
 static int fill_io(ms_env* env, const ms_actions* act, const ms_obs_out* obs, const ms_reward_out* rew,
                    const ms_event_out* ev, ms::StepIO* out);
 static int check_mlp(const ms_mlp_params* p, int32_t obs_stride, int32_t n_units, int32_t units_per_group);
@@ -325,9 +326,9 @@ int ms_env_step_act(ms_env* env, const ms_actions* act, const ms_obs_out* obs, c
     return env_step_impl(env, act, obs, rew, ev, &fa, nullptr, stream);
 }
 
-int ms_env_rollout_act(ms_env* env, const ms_actions* act, const ms_obs_out* obs, const ms_reward_out* rew,
-                       const ms_event_out* ev, const ms_fused_act* next, const ms_round_strides* strides,
-                       int32_t n_rounds, int32_t act_after_last, void* stream) {
+static int rollout_act_impl(ms_env* env, const ms_actions* act, const ms_obs_out* obs, const ms_reward_out* rew,
+                            const ms_event_out* ev, const ms_fused_act* next, const ms_round_strides* strides,
+                            int32_t n_rounds, int32_t act_after_last, uint64_t hc_mask, void* stream) {
     ms::FusedAct fa;
     const int rc = fused_act_args(env, act, obs, ev, next, "ms_env_rollout_act", &fa);
     if (rc != MS_OK) return rc;
@@ -341,7 +342,45 @@ int ms_env_rollout_act(ms_env* env, const ms_actions* act, const ms_obs_out* obs
                     r.acceptor_reward, r.agent_reward, r.auctioneer_reward, r.next_off_action, r.next_off_logprob,
                     r.next_acc_action, r.next_acc_logprob, r.offset_step},
                    n_rounds, act_after_last ? 1 : 0};
-    return env_step_impl(env, act, obs, rew, ev, &fa, &ro, stream);
+    const ms::MixIO mx{hc_mask, nullptr, nullptr};
+    return env_step_impl(env, act, obs, rew, ev, &fa, &ro, stream, &mx);
+}
+
+int ms_env_rollout_act(ms_env* env, const ms_actions* act, const ms_obs_out* obs, const ms_reward_out* rew,
+                       const ms_event_out* ev, const ms_fused_act* next, const ms_round_strides* strides,
+                       int32_t n_rounds, int32_t act_after_last, void* stream) {
+    return rollout_act_impl(env, act, obs, rew, ev, next, strides, n_rounds, act_after_last, 0, stream);
+}
+
+// the mixed fused calls' own checks (before fused_act_args'): fixed prices, both action arrays, the mask's range
+static int fused_mixed_check(const ms_env* env, const ms_actions* act, uint64_t hc_mask, const char* who) {
+    if (!env || !act) return fail(MS_EINVAL, "%s: env/actions is NULL", who);
+    if (env->cfg.free_prices) return fail(MS_EINVAL, "%s: the hard-coded agents are fixed-price only", who);
+    if (!act->acceptor || !act->offer_core)
+        return fail(MS_EINVAL, "%s: acceptor and offer_core actions must both be given", who);
+    const int N = env->P.N;
+    if (N < MS_MAX_AGENTS && (hc_mask >> N) != 0)
+        return fail(MS_EINVAL, "%s: hc_mask has a bit at or above n_agents (%d)", who, N);
+    return MS_OK;
+}
+
+int ms_env_step_act_mixed(ms_env* env, const ms_actions* act, const ms_obs_out* obs, const ms_reward_out* rew,
+                          const ms_event_out* ev, const ms_fused_act* next, uint64_t hc_mask, void* stream) {
+    int rc = fused_mixed_check(env, act, hc_mask, "ms_env_step_act_mixed");
+    if (rc != MS_OK) return rc;
+    ms::FusedAct fa;
+    rc = fused_act_args(env, act, obs, ev, next, "ms_env_step_act_mixed", &fa);
+    if (rc != MS_OK) return rc;
+    const ms::MixIO mx{hc_mask, nullptr, nullptr};
+    return env_step_impl(env, act, obs, rew, ev, &fa, nullptr, stream, &mx);
+}
+
+int ms_env_rollout_act_mixed(ms_env* env, const ms_actions* act, const ms_obs_out* obs, const ms_reward_out* rew,
+                             const ms_event_out* ev, const ms_fused_act* next, const ms_round_strides* strides,
+                             int32_t n_rounds, int32_t act_after_last, uint64_t hc_mask, void* stream) {
+    const int rc = fused_mixed_check(env, act, hc_mask, "ms_env_rollout_act_mixed");
+    if (rc != MS_OK) return rc;
+    return rollout_act_impl(env, act, obs, rew, ev, next, strides, n_rounds, act_after_last, hc_mask, stream);
 }
 
 int ms_env_step_act_supported(const ms_env* env) {
@@ -367,11 +406,13 @@ static int env_step_impl(ms_env* env, const ms_actions* act, const ms_obs_out* o
     ms::StepIO io{};
     const int rc = fill_io(env, act, obs, rew, ev, &io);
     if (rc != MS_OK) return rc;
+    // (the fused launches take the mask alone: their rounds write the rules' picks into the action arrays)
     if (ro)
         HIP_TRY(ms::launch_env_rollout_act(env->P, env->E, env->recs, env->mt, env->liab, io, *fa, ro->st, ro->n_rounds,
-                                           ro->act_last, (hipStream_t)stream));
+                                           ro->act_last, mix ? mix->hc_mask : 0, (hipStream_t)stream));
     else if (fa)
-        HIP_TRY(ms::launch_env_step_act(env->P, env->E, env->recs, env->mt, env->liab, io, *fa, (hipStream_t)stream));
+        HIP_TRY(ms::launch_env_step_act(env->P, env->E, env->recs, env->mt, env->liab, io, *fa,
+                                        mix ? mix->hc_mask : 0, (hipStream_t)stream));
     else
         HIP_TRY(ms::launch_env_step(env->P, env->E, env->recs, env->mt, env->liab, io, mix ? *mix : ms::MixIO{},
                                     (hipStream_t)stream));
@@ -1252,6 +1293,26 @@ int ms_adam_step_dev(const ms_adam_tensor* tensors, int32_t n_tensors, const dou
     }
     HIP_TRY(ms::launch_adam(reinterpret_cast<const ms::AdamTensor*>(tensors), n_tensors, lr, n_lr, 0, beta1, beta2, eps,
                             step_dev, (hipStream_t)stream));
+    return MS_OK;
+}
+
+int ms_adam_step_dev_masked(const ms_adam_tensor* tensors, int32_t n_tensors, const double* lr, int32_t n_lr,
+                            const int64_t* step_dev, double beta1, double beta2, double eps, int32_t n_groups,
+                            const uint8_t* frozen_dev, void* stream) {
+    if (!tensors || !lr || !step_dev) return fail(MS_EINVAL, "NULL argument");
+    if (n_tensors < 1 || n_tensors > MS_ADAM_MAX_TENSORS) return fail(MS_EINVAL, "n_tensors must be in [1, %d]", MS_ADAM_MAX_TENSORS);
+    if (n_lr < 1 || n_lr > ms::kAdamMaxGroups) return fail(MS_EINVAL, "n_lr must be in [1, %d]", ms::kAdamMaxGroups);
+    if (frozen_dev && n_groups < 1) return fail(MS_EINVAL, "ms_adam_step_dev_masked: n_groups must be >= 1");
+    for (int i = 0; i < n_tensors; i++) {
+        const ms_adam_tensor& t = tensors[i];
+        if (!t.param || !t.grad || !t.exp_avg || !t.exp_avg_sq || t.numel < 0) return fail(MS_EINVAL, "bad tensor %d", i);
+        if (t.lr_group < 0 || t.lr_group >= n_lr) return fail(MS_EINVAL, "tensor %d: lr_group out of range", i);
+        if (frozen_dev && (t.numel < n_groups || t.numel % n_groups != 0))
+            return fail(MS_EINVAL, "ms_adam_step_dev_masked: tensor %d's %lld elements do not split into %d groups", i,
+                        (long long)t.numel, n_groups);
+    }
+    HIP_TRY(ms::launch_adam(reinterpret_cast<const ms::AdamTensor*>(tensors), n_tensors, lr, n_lr, 0, beta1, beta2, eps,
+                            step_dev, (hipStream_t)stream, frozen_dev, n_groups));
     return MS_OK;
 }
 

@@ -1038,7 +1038,9 @@ constexpr int kLiabPrefetch = 4;  // newest chain entries loaded ahead per core 
 // (the m_add sites and the rank-ordered executions they need) on a plain round, for the fused kernels given
 // io.metrics: none of EXT's hard-coded agents, full acceptor rows or generic shape. SEQ: the round is one of
 // several in its launch, so quality_sum is added by the leader's ordered read-modify-write (m_load / m_store).
-template <int LPE, bool EXT, bool CMP, class SH, bool MET = EXT, bool SEQ = false>
+// HC (the mixed fused kernels, not EXT): the agents of mix->hc_mask play the rules as under EXT, and the rows the
+// round used for them are written back over the supplied ones (io.act_acc / io.act_off: the trainer's ring slot).
+template <int LPE, bool EXT, bool CMP, class SH, bool MET = EXT, bool SEQ = false, bool HC = false>
 __device__ __forceinline__ void env_round(const Params& P, int64_t E, uint8_t* recs, uint32_t* mt, Liab* liab,
                                           const StepIO& io, int64_t slot, int lane_arg = -1,
                                           uint8_t* wave_lds = nullptr, const int8_t* acc_lds = nullptr,
@@ -1177,6 +1179,7 @@ __device__ __forceinline__ void env_round(const Params& P, int64_t E, uint8_t* r
     // this round's episode accumulators (trainPPO.py:172-187): slot of episode round / episodeLength
     uint64_t hc_mask = 0;  // the agents that play the rules: all without supplied actions, else mix's
     if constexpr (EXT) hc_mask = io.act_acc == nullptr ? ~0ull : (mix ? mix->hc_mask : 0ull);
+    if constexpr (HC) hc_mask = mix->hc_mask;
     constexpr bool MX = MET;
     ms_env_metrics* mx = (MX && io.metrics && active)
                              ? io.metrics + (int64_t)((round / P.ep_len) % io.metrics_slots) * E + e
@@ -1219,6 +1222,18 @@ __device__ __forceinline__ void env_round(const Params& P, int64_t E, uint8_t* r
                 for (int i = gl; i < N * C; i += LPE) mix->acc_taken[e * N * C + i] = a_acc[i];
             if (mix->off_taken)
                 for (int i = gl; i < NL; i += LPE) mix->off_taken[e * NL + i] = a_off[i];
+        }
+    }
+    if constexpr (HC) {
+        // the masked agents' rows of the action arrays become what the round plays (the rules' picks); the other
+        // rows and the padding groups' replica are left as they are
+        if (active) {
+            int8_t* r_acc = const_cast<int8_t*>(io.act_acc) + e * N * C;
+            int8_t* r_off = const_cast<int8_t*>(io.act_off) + e * NL;
+            for (int i = gl; i < N * C; i += LPE)
+                if ((hc_mask >> (i / C)) & 1ull) r_acc[i] = a_acc[i];
+            for (int i = gl; i < NL; i += LPE)
+                if ((hc_mask >> (i / L)) & 1ull) r_off[i] = a_off[i];
         }
     }
     if (!io.act_auct) {
@@ -1911,6 +1926,24 @@ __global__ void __launch_bounds__(64, 4) k_env_step_act(Params P, int64_t E, uin
     }
 }
 
+// k_env_step_act with a mixed population (ms_env_step_act_mixed): the agents of hc_mask play the rules in the
+// round, and their rows of the round's action arrays receive the picks
+template <int LPE, class SH, bool MET = false>
+__global__ void __launch_bounds__(64, 4) k_env_step_act_mixed(Params P, int64_t E, uint8_t* recs, uint32_t* mt,
+                                                           Liab* liab, StepIO io, FusedAct fa, uint64_t hc_mask) {
+    if (io.span && threadIdx.x == 0) {
+        io.span[4 * blockIdx.x] = __builtin_amdgcn_s_memrealtime();
+        io.span[4 * blockIdx.x + 2] = __builtin_amdgcn_s_memtime();
+    }
+    const MixIO mix{hc_mask, nullptr, nullptr};
+    env_round<LPE, false, true, SH, MET, false, true>(P, E, recs, mt, liab, io, blockIdx.x, -1, nullptr, nullptr, &mix);
+    fused_act<LPE, SH>(P, E, fa, blockIdx.x);
+    if (io.span && threadIdx.x == 0) {
+        io.span[4 * blockIdx.x + 3] = __builtin_amdgcn_s_memtime();
+        io.span[4 * blockIdx.x + 1] = __builtin_amdgcn_s_memrealtime();
+    }
+}
+
 template <class T>
 __device__ __forceinline__ T* advance(T* p, int64_t bytes) {
     return p ? reinterpret_cast<T*>(reinterpret_cast<uintptr_t>(p) + bytes) : p;
@@ -1961,6 +1994,66 @@ __global__ void __launch_bounds__(64, 2) k_env_rollout_act(RolloutArgs A0) {
         io.rew_agent = advance(io.rew_agent, t * st.rew_agent);
         io.rew_auct = advance(io.rew_auct, t * st.rew_auct);
         env_round<LPE, false, true, SH, MET, MET>(A.P, A.E, A.recs, A.mt, A.liab, io, blockIdx.x, lane);
+        if (t + 1 < n_rounds || A.act_last) {
+            FusedAct fa = A.fa;
+            fa.off_action = advance(fa.off_action, t * st.off_action);
+            fa.off_logprob = advance(fa.off_logprob, t * st.off_logprob);
+            fa.acc_action = advance(fa.acc_action, t * st.acc_action);
+            fa.acc_logprob = advance(fa.acc_logprob, t * st.acc_logprob);
+            fa.off_offset += (uint64_t)t * st.offset_step;
+            fa.acc_offset += (uint64_t)t * st.offset_step;
+            fused_act<LPE, SH>(A.P, A.E, fa, blockIdx.x, lane);
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+        wave_sync();
+    }
+    if (span && threadIdx.x == 0) {
+        span[4 * blockIdx.x + 3] = __builtin_amdgcn_s_memtime();
+        span[4 * blockIdx.x + 1] = __builtin_amdgcn_s_memrealtime();
+    }
+}
+
+// k_env_rollout_act with a mixed population (ms_env_rollout_act_mixed), the one mask for every round and replica:
+// each round substitutes the masked agents' actions by the rules and writes them into its action ring slot; the
+// acting samples every unit as ever, and the next round overrides the masked ones. A kernel of its own with the
+// loop written out again, not a shared body: moving k_env_rollout_act's loop into a function both kernels call
+// changed that kernel's register allocation and schedule (same resource figures, other code), and the plain
+// rollout is to compile to exactly what it did before the mixed one existed (profiles/r14_mixed_train).
+struct RolloutMixArgs {
+    RolloutArgs R;
+    uint64_t hc_mask;
+};
+template <int LPE, class SH, bool MET = false>
+__global__ void __launch_bounds__(64, 2) k_env_rollout_act_mixed(RolloutMixArgs A0) {
+    unsigned long long* span = A0.R.io.span;
+    if (span && threadIdx.x == 0) {
+        span[4 * blockIdx.x] = __builtin_amdgcn_s_memrealtime();
+        span[4 * blockIdx.x + 2] = __builtin_amdgcn_s_memtime();
+    }
+    const int n_rounds = A0.R.n_rounds;
+    for (int t = 0; t < n_rounds; t++) {
+        auto ka = __builtin_amdgcn_kernarg_segment_ptr();  // (see k_env_rollout_act)
+        asm volatile("" : "+s"(ka));
+        const RolloutMixArgs& M = *(const RolloutMixArgs*)ka;
+        const RolloutArgs& A = M.R;
+        int lane = threadIdx.x;
+        asm volatile("" : "+v"(lane));
+        const RoundStride& st = A.st;
+        StepIO io = A.io;
+        io.span = nullptr;
+        io.act_acc = advance(io.act_acc, t * st.act_acc);
+        io.act_off = advance(io.act_off, t * st.act_off);
+        io.obs_crow = advance(io.obs_crow, t * st.obs_crow);
+        io.obs_cown = advance(io.obs_cown, t * st.obs_cown);
+        io.obs_off = advance(io.obs_off, t * st.obs_off);
+        io.rew_offer = advance(io.rew_offer, t * st.rew_offer);
+        io.rew_acc = advance(io.rew_acc, t * st.rew_acc);
+        io.rew_agent = advance(io.rew_agent, t * st.rew_agent);
+        io.rew_auct = advance(io.rew_auct, t * st.rew_auct);
+        const MixIO mix{M.hc_mask, nullptr, nullptr};
+        env_round<LPE, false, true, SH, MET, MET, true>(A.P, A.E, A.recs, A.mt, A.liab, io, blockIdx.x, lane, nullptr,
+                                                        nullptr, &mix);
         if (t + 1 < n_rounds || A.act_last) {
             FusedAct fa = A.fa;
             fa.off_action = advance(fa.off_action, t * st.off_action);
@@ -2991,55 +3084,72 @@ bool env_step_act_supported(const Params& P, int64_t E) {
 }
 template <int LPE, class SH>
 static hipError_t launch_step_act_sh(const Params& P, int64_t E, uint8_t* recs, uint32_t* mt, Liab* liab,
-                                     const StepIO& io, const FusedAct& fa, hipStream_t s) {
+                                     const StepIO& io, const FusedAct& fa, uint64_t hc_mask, hipStream_t s) {
     constexpr int G = kWave / LPE;
     const int64_t blocks = (E + G - 1) / G;
     const size_t lds = (size_t)P.s_total * G > 4 * kMtN ? (size_t)P.s_total * G : 4 * kMtN;
+    if (hc_mask) {  // a mixed population (ms_env_step_act_mixed); no mask: the plain kernels
+        auto kern = io.metrics ? k_env_step_act_mixed<LPE, SH, true> : k_env_step_act_mixed<LPE, SH, false>;
+        hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(kWave), lds, s, P, E, recs, mt, liab, io, fa, hc_mask);
+        return hipGetLastError();
+    }
     auto kern = io.metrics ? k_env_step_act<LPE, SH, true> : k_env_step_act<LPE, SH, false>;
     hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(kWave), lds, s, P, E, recs, mt, liab, io, fa);
     return hipGetLastError();
 }
+// hc_mask (here and in launch_env_rollout_act): the agents that play the rules in the rounds, 0 for none
 hipError_t launch_env_step_act(const Params& P, int64_t E, uint8_t* recs, uint32_t* mt, Liab* liab, const StepIO& io,
-                               const FusedAct& fa, hipStream_t s) {
+                               const FusedAct& fa, uint64_t hc_mask, hipStream_t s) {
     if (!env_step_act_supported(P, E) || io.act_acc == nullptr || io.obs_acc != nullptr) return hipErrorInvalidValue;
+    if (hc_mask && (io.act_off == nullptr || P.free_prices)) return hipErrorInvalidValue;
     switch (lanes_per_env(P, E)) {
-        case 16: return launch_step_act_sh<16, DynShape>(P, E, recs, mt, liab, io, fa, s);
+        case 16: return launch_step_act_sh<16, DynShape>(P, E, recs, mt, liab, io, fa, hc_mask, s);
         case 32:
 #ifndef MS_NO_FIXED_SHAPES
-            if (is_shape<4, 4, 3, 1>(P)) return launch_step_act_sh<32, FixShape<4, 4, 3, 1>>(P, E, recs, mt, liab, io, fa, s);
+            if (is_shape<4, 4, 3, 1>(P))
+                return launch_step_act_sh<32, FixShape<4, 4, 3, 1>>(P, E, recs, mt, liab, io, fa, hc_mask, s);
 #endif
-            return launch_step_act_sh<32, DynShape>(P, E, recs, mt, liab, io, fa, s);
-        default: return launch_step_act_sh<64, DynShape>(P, E, recs, mt, liab, io, fa, s);
+            return launch_step_act_sh<32, DynShape>(P, E, recs, mt, liab, io, fa, hc_mask, s);
+        default: return launch_step_act_sh<64, DynShape>(P, E, recs, mt, liab, io, fa, hc_mask, s);
     }
 }
 template <int LPE, class SH>
 static hipError_t launch_rollout_act_sh(const Params& P, int64_t E, uint8_t* recs, uint32_t* mt, Liab* liab,
                                         const StepIO& io, const FusedAct& fa, const RoundStride& st, int n_rounds,
-                                        int act_last, hipStream_t s) {
+                                        int act_last, uint64_t hc_mask, hipStream_t s) {
     constexpr int G = kWave / LPE;
     const int64_t blocks = (E + G - 1) / G;
     const size_t lds = (size_t)P.s_total * G > 4 * kMtN ? (size_t)P.s_total * G : 4 * kMtN;
     const RolloutArgs A{P, E, recs, mt, liab, io, fa, st, n_rounds, act_last};
+    if (hc_mask) {  // a mixed population (ms_env_rollout_act_mixed)
+        const RolloutMixArgs M{A, hc_mask};
+        auto kern = io.metrics ? k_env_rollout_act_mixed<LPE, SH, true> : k_env_rollout_act_mixed<LPE, SH, false>;
+        hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(kWave), lds, s, M);
+        return hipGetLastError();
+    }
     auto kern = io.metrics ? k_env_rollout_act<LPE, SH, true> : k_env_rollout_act<LPE, SH, false>;
     hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(kWave), lds, s, A);
     return hipGetLastError();
 }
 hipError_t launch_env_rollout_act(const Params& P, int64_t E, uint8_t* recs, uint32_t* mt, Liab* liab,
                                   const StepIO& io, const FusedAct& fa, const RoundStride& st, int n_rounds,
-                                  int act_last, hipStream_t s) {
+                                  int act_last, uint64_t hc_mask, hipStream_t s) {
     if (!env_step_act_supported(P, E) || io.act_acc == nullptr || io.obs_acc != nullptr || io.ev_acc != nullptr ||
         io.ev_term != nullptr || n_rounds < 1)
         return hipErrorInvalidValue;
+    if (hc_mask && (io.act_off == nullptr || P.free_prices)) return hipErrorInvalidValue;
     switch (lanes_per_env(P, E)) {
-        case 16: return launch_rollout_act_sh<16, DynShape>(P, E, recs, mt, liab, io, fa, st, n_rounds, act_last, s);
+        case 16:
+            return launch_rollout_act_sh<16, DynShape>(P, E, recs, mt, liab, io, fa, st, n_rounds, act_last, hc_mask, s);
         case 32:
 #ifndef MS_NO_FIXED_SHAPES
             if (is_shape<4, 4, 3, 1>(P))
                 return launch_rollout_act_sh<32, FixShape<4, 4, 3, 1>>(P, E, recs, mt, liab, io, fa, st, n_rounds,
-                                                                       act_last, s);
+                                                                       act_last, hc_mask, s);
 #endif
-            return launch_rollout_act_sh<32, DynShape>(P, E, recs, mt, liab, io, fa, st, n_rounds, act_last, s);
-        default: return launch_rollout_act_sh<64, DynShape>(P, E, recs, mt, liab, io, fa, st, n_rounds, act_last, s);
+            return launch_rollout_act_sh<32, DynShape>(P, E, recs, mt, liab, io, fa, st, n_rounds, act_last, hc_mask, s);
+        default:
+            return launch_rollout_act_sh<64, DynShape>(P, E, recs, mt, liab, io, fa, st, n_rounds, act_last, hc_mask, s);
     }
 }
 // ms_env_rollout_act_free: 16 lanes per replica (max(N, C) <= 16), one wave per agent (N <= 8: a 512-lane

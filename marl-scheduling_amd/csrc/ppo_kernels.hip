@@ -2017,10 +2017,41 @@ __global__ void __launch_bounds__(256) k_adam(AdamArgs a) {
     }
 }
 
+// k_adam with frozen groups (ms_adam_step_dev_masked): every tensor is [n_groups][numel / n_groups]; the elements
+// of a group g with frozen[g] != 0 are skipped whole, so its parameters and both moments keep their bits whatever
+// the gradient holds. The same arithmetic as k_adam, statement for statement (a kernel of its own, so k_adam
+// compiles to what it did without it).
+__global__ void __launch_bounds__(256) k_adam_masked(AdamArgs a, const uint8_t* frozen, int n_groups) {
+    const AdamTensor& t = a.t[blockIdx.y];
+    float ns = a.neg_step[t.lr_group], bc2_sqrt = a.bc2_sqrt;
+    if (a.step_dev) {
+        const double step = (double)*a.step_dev;
+        const double bc1 = 1.0 - pow(a.beta1d, step), bc2 = 1.0 - pow(a.beta2d, step);
+        ns = (float)((a.lr[t.lr_group] / bc1) * -1.0);
+        bc2_sqrt = (float)sqrt(bc2);
+    }
+    const int64_t per_group = t.numel / n_groups;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < t.numel; i += (int64_t)gridDim.x * 256) {
+        if (frozen[i / per_group]) continue;
+        const float g = t.grad[i];
+        float m = t.exp_avg[i], v = t.exp_avg_sq[i];
+        m = m + a.w1 * (g - m);
+        v = v * a.beta2;
+        v = v + a.one_m_beta2 * (g * g);
+        const float den = sqrtf(v) / bc2_sqrt + a.eps;
+        t.param[i] = t.param[i] + ns * (m / den);
+        t.exp_avg[i] = m;
+        t.exp_avg_sq[i] = v;
+    }
+}
+
 hipError_t launch_adam(const AdamTensor* ts, int n, const double* lr, int n_lr, int64_t step, double beta1,
-                       double beta2, double eps, const int64_t* step_dev, hipStream_t st) {
+                       double beta2, double eps, const int64_t* step_dev, hipStream_t st, const uint8_t* frozen,
+                       int n_groups) {
+    // frozen (device, [n_groups] bytes; NULL: none): the groups the step leaves untouched (k_adam_masked)
     if (n < 1 || n > kAdamMaxTensors || n_lr < 1 || n_lr > kAdamMaxGroups || (step < 1 && !step_dev))
         return hipErrorInvalidValue;
+    if (frozen && n_groups < 1) return hipErrorInvalidValue;
     if (step_dev) step = 1;  // the host-side corrections are unused
     AdamArgs a{};
     a.step_dev = step_dev;
@@ -2030,6 +2061,7 @@ hipError_t launch_adam(const AdamTensor* ts, int n, const double* lr, int n_lr, 
     int64_t mx = 1;
     for (int i = 0; i < n; i++) {
         if (ts[i].lr_group < 0 || ts[i].lr_group >= n_lr) return hipErrorInvalidValue;
+        if (frozen && (ts[i].numel < n_groups || ts[i].numel % n_groups != 0)) return hipErrorInvalidValue;
         a.t[i] = ts[i];
         mx = ts[i].numel > mx ? ts[i].numel : mx;
     }
@@ -2043,7 +2075,10 @@ hipError_t launch_adam(const AdamTensor* ts, int n, const double* lr, int n_lr, 
     a.bc2_sqrt = (float)sqrt(bc2);
     int64_t bx = (mx + 255) / 256;
     bx = bx > 1024 ? 1024 : bx;
-    hipLaunchKernelGGL(k_adam, dim3((unsigned)bx, (unsigned)n), dim3(256), 0, st, a);
+    if (frozen)
+        hipLaunchKernelGGL(k_adam_masked, dim3((unsigned)bx, (unsigned)n), dim3(256), 0, st, a, frozen, n_groups);
+    else
+        hipLaunchKernelGGL(k_adam, dim3((unsigned)bx, (unsigned)n), dim3(256), 0, st, a);
     return hipGetLastError();
 }
 

@@ -153,7 +153,7 @@ class BatchedEnv:
         return obs
 
     def step(self, acceptor, offer_core, offer_price=None, auctioneer=None, obs=None, rewards=None, events=None,
-             stream=None, next_act=None):
+             stream=None, next_act=None, hardcoded=None):
         """One round of SchedulingEnv.step (SchedulingEnvironment.py:32-83) for all replicas.
 
         acceptor [E,N,C] int8, offer_core [E,N,L] int8, offer_price [E,N,L] int8
@@ -161,7 +161,15 @@ class BatchedEnv:
         HardcodedAuctioneerAcceptor. Returns (obs, rewards, events) dicts.
         next_act (an abi.MsFusedAct): the next round's acting fused into the round (ms_env_step_act; fixed
         prices, compact acceptor observations; see fused_act_supported).
+        hardcoded (with next_act; agent indices or an int mask, see hardcoded_mask): those agents play the rules in
+        the round (ms_env_step_act_mixed, see fused_mixed_supported) and their rows of acceptor / offer_core
+        receive the actions the round used. An empty mask goes through the same library call, which then runs
+        the round of the call without the argument.
         """
+        mask = 0 if hardcoded is None else self._fused_mask(hardcoded, "ms_env_step_act_mixed")
+        if mask and next_act is None:
+            raise ValueError("step: hardcoded goes with next_act (a round alone: step_mixed)")
+        mixed = hardcoded is not None and next_act is not None and has("ms_env_step_act_mixed")
         for t in (acceptor, offer_core, offer_price, auctioneer):
             if t is not None:
                 assert t.dtype == torch.int8 and t.is_contiguous() and t.device == self.device
@@ -176,13 +184,39 @@ class BatchedEnv:
         obs = self.obs_buffers() if obs is None else obs
         rewards = self.reward_buffers() if rewards is None else rewards
         a, o, r, ev = self._step_structs(acceptor, offer_core, offer_price, auctioneer, obs, rewards, events)
-        if next_act is not None:
+        if mixed:
+            check(lib.ms_env_step_act_mixed(self._h, ct.byref(a), ct.byref(o), ct.byref(r),
+                                            ct.byref(ev) if ev else None, ct.byref(next_act), mask,
+                                            stream_ptr(stream)))
+        elif next_act is not None:
             check(lib.ms_env_step_act(self._h, ct.byref(a), ct.byref(o), ct.byref(r), ct.byref(ev) if ev else None,
                                       ct.byref(next_act), stream_ptr(stream)))
         else:
             check(lib.ms_env_step(self._h, ct.byref(a), ct.byref(o), ct.byref(r), ct.byref(ev) if ev else None,
                                   stream_ptr(stream)))
         return obs, rewards, events
+
+    def step_act(self, acceptor, offer_core, next_act, obs=None, rewards=None, events=None, stream=None,
+                 hardcoded=None):
+        """step(next_act=...): the fixed-price round with the next round's acting fused in, optionally with a
+        mixed population (hardcoded)."""
+        return self.step(acceptor, offer_core, obs=obs, rewards=rewards, events=events, stream=stream,
+                         next_act=next_act, hardcoded=hardcoded)
+
+    def fused_mixed_supported(self) -> bool:
+        """Whether step(next_act=..., hardcoded=...) and rollout_act(hardcoded=...) can run this env's rounds:
+        fused_act_supported and a library with the mixed fused calls (ABI 24). False: a caller steps a mixed
+        population with an act launch and step_mixed per round."""
+        return (has("ms_env_step_act_mixed") and has("ms_env_rollout_act_mixed") and not self.free_prices and
+                self.fused_act_supported())
+
+    def _fused_mask(self, hardcoded, symbol: str) -> int:
+        if self.free_prices:
+            raise ValueError("the hard-coded agents are fixed-price only")
+        mask = self.hardcoded_mask(hardcoded)
+        if mask and not has(symbol):
+            raise RuntimeError("the loaded libmarlsched.so has no %s (ABI < 24)" % symbol)
+        return mask
 
     def hardcoded_mask(self, hardcoded_agents) -> int:
         """The ms_mixed.hardcoded_agents mask of an iterable of agent indices (0-based) or an int mask;
@@ -206,7 +240,8 @@ class BatchedEnv:
         (Agent.py:630-641) in the kernel, on the env stream before the auctioneer, in ascending index; the others
         play their rows of acceptor [E,N,C] / offer_core [E,N,L], which must both be given (a masked agent's rows
         are ignored whatever they hold). taken: an optional dict(acceptor=[E,N,C] int8, offer_core=[E,N,L] int8)
-        that receives the actions the round used. Returns (obs, rewards, events) like step."""
+        that receives the actions the round used; its tensors may be the supplied acceptor / offer_core themselves,
+        which then hold the played trajectory. Returns (obs, rewards, events) like step."""
         if self.free_prices:
             raise ValueError("step_mixed: the hard-coded agents are fixed-price only")
         if not has("ms_env_step_mixed"):
@@ -255,14 +290,20 @@ class BatchedEnv:
         return rings
 
     def rollout_act(self, acceptor, offer_core, obs, rewards, next_act, strides, n_rounds, act_after_last=False,
-                    events=None, stream=None, next_out=None):
+                    events=None, stream=None, next_out=None, hardcoded=None):
         """n_rounds rounds of step(next_act=...) in one launch (ms_env_rollout_act): round t reads and
         writes the given arrays advanced by t * strides (an abi.MsRoundStrides, bytes) and acts with the
         Philox offsets + t * strides.offset_step. Bit-identical to the n_rounds step calls.
         next_out: the tensors behind next_act's outputs, dict(off_action, off_logprob, acc_action, acc_logprob)
         (round 0's slots), bounds-checked like the other rings when given.
         events: launch_span and / or metrics (a metrics_buffer: every round adds into the slot of its own
-        episode, as n_rounds step calls would, bit for bit; ABI 21); no accepted / terminated records."""
+        episode, as n_rounds step calls would, bit for bit; ABI 21); no accepted / terminated records.
+        hardcoded (agent indices or an int mask): a mixed population in every round (ms_env_rollout_act_mixed):
+        round t's acceptor / offer_core slots receive the masked agents' played actions, and the masked units'
+        log-probs in next_act's outputs belong to no played action. An empty mask goes through the same library
+        call, which then runs the rounds of the call without the argument."""
+        mask = 0 if hardcoded is None else self._fused_mask(hardcoded, "ms_env_rollout_act_mixed")
+        mixed = hardcoded is not None and has("ms_env_rollout_act_mixed")
         for t in (acceptor, offer_core):
             assert t.dtype == torch.int8 and t.device == self.device
         rings = self._ring_list(acceptor, offer_core, obs, rewards, strides)
@@ -274,6 +315,11 @@ class BatchedEnv:
                               (next_out["acc_logprob"], strides.next_acc_logprob, torch.float32)], n_act)
         self.check_rings(rings, n_rounds)
         a, o, r, ev = self._step_structs(acceptor, offer_core, None, None, obs, rewards, events)
+        if mixed:
+            check(lib.ms_env_rollout_act_mixed(self._h, ct.byref(a), ct.byref(o), ct.byref(r),
+                                               ct.byref(ev) if ev else None, ct.byref(next_act), ct.byref(strides),
+                                               int(n_rounds), int(bool(act_after_last)), mask, stream_ptr(stream)))
+            return
         check(lib.ms_env_rollout_act(self._h, ct.byref(a), ct.byref(o), ct.byref(r), ct.byref(ev) if ev else None,
                                      ct.byref(next_act), ct.byref(strides), int(n_rounds), int(bool(act_after_last)),
                                      stream_ptr(stream)))

@@ -67,6 +67,13 @@ def episode_values(m: np.ndarray, cfg: abi.MsConfig, episode_length: int, n_agen
     return out
 
 
+def split_agent_rew(agent_rew, hardcoded) -> tuple:
+    """(mean agentRew of the rule-based agents `hardcoded`, mean of the others), None for an empty side."""
+    hc = sorted(set(int(a) for a in hardcoded))
+    rest = [a for a in range(len(agent_rew)) if a not in hc]
+    return (float(np.mean(agent_rew[hc])) if hc else None, float(np.mean(agent_rew[rest])) if rest else None)
+
+
 LIST_KEYS = ("acceptorRew", "coreChooserRew", "priceChooserRew", "prices", "auctioneerRew", "dwellTimes",
              "agentRew", "acceptionQuality", "acceptionAmount", "terminationRevenues", "tradeRevenues")
 

@@ -28,7 +28,7 @@ import torch.nn as nn
 from torch.distributions import Categorical
 
 from . import abi
-from ._lib import check, lib, ptr, stream_ptr
+from ._lib import check, has, lib, ptr, stream_ptr
 
 MS_EINVAL = 22  # include/marlsched.h
 
@@ -411,9 +411,11 @@ class HipAdam:
     """torch.optim.Adam (defaults betas (0.9, 0.999), eps 1e-8, no weight decay) over the
     parameters of one PPOGroup as one ``ms_adam_step`` launch per step: tensor i of
     ``param_groups[k]["params"]`` uses ``param_groups[k]["lr"]`` like torch's param groups
-    (PPOmodules.py:100-105). The state (exp_avg, exp_avg_sq, step) mirrors torch's."""
+    (PPOmodules.py:100-105). The state (exp_avg, exp_avg_sq, step) mirrors torch's.
+    freeze(frozen, n_groups): the nets' groups a step skips (ms_adam_step_dev_masked)."""
 
     def __init__(self, param_groups, betas=(0.9, 0.999), eps=1e-8):
+        self.frozen = None  # (device uint8 [n_groups], n_groups): see freeze
         self.param_groups = [dict(params=list(g["params"]), lr=float(g["lr"])) for g in param_groups]
         self.betas, self.eps = betas, eps
         self.step_count = 0
@@ -434,6 +436,24 @@ class HipAdam:
             for p in g["params"]:
                 p.grad = None
 
+    def freeze(self, frozen, n_groups: int):
+        """From now on step() leaves the groups g with frozen[g] alone (every parameter is stacked over the
+        n_groups groups on its leading axis): their weights and both moments keep their bits whatever the gradient
+        holds; the shared step count advances as ever, which the frozen groups never read. None / all False: no
+        group is frozen."""
+        flags = [bool(f) for f in (frozen if frozen is not None else [])]
+        if not any(flags):
+            self.frozen = None
+            return
+        if not has("ms_adam_step_dev_masked"):
+            raise RuntimeError("the loaded libmarlsched.so has no ms_adam_step_dev_masked (ABI < 24)")
+        assert len(flags) == n_groups
+        for g in self.param_groups:
+            for p in g["params"]:
+                assert p.shape[0] == n_groups, "parameters are stacked over the groups"
+        dev = self.param_groups[0]["params"][0].device
+        self.frozen = (torch.tensor(flags, dtype=torch.uint8, device=dev), int(n_groups))
+
     @torch.no_grad()
     def step(self, stream=None):
         self.step_count += 1
@@ -453,6 +473,11 @@ class HipAdam:
             return
         arr = (abi.MsAdamTensor * len(ts))(*ts)
         lrs = (ct.c_double * len(self.param_groups))(*[g["lr"] for g in self.param_groups])
+        if self.frozen is not None:
+            check(lib.ms_adam_step_dev_masked(arr, len(ts), lrs, len(self.param_groups), ptr(self.step_dev),
+                                              self.betas[0], self.betas[1], self.eps, self.frozen[1],
+                                              ptr(self.frozen[0]), stream_ptr(stream)))
+            return
         check(lib.ms_adam_step_dev(arr, len(ts), lrs, len(self.param_groups), ptr(self.step_dev), self.betas[0],
                                    self.betas[1], self.eps, stream_ptr(stream)))
 

@@ -161,7 +161,14 @@ class Trainer:
     def __init__(self, cfg: abi.MsConfig, n_envs: int, arch: str = "local", hyper: Hyper | None = None, seed: int = 0,
                  device=None, rank: int = 0, world_size: int = 1, process_group=None, fused: bool = True,
                  use_graph: bool = True, common_rows: bool = True, rollout_streams: int = 1, metrics: bool = False,
-                 episode_length: int | None = None, compact: bool = True):
+                 episode_length: int | None = None, compact: bool = True, hardcoded_agents=None):
+        """hardcoded_agents (an iterable of 0-based agent indices; fixed prices): train in a mixed market. The given
+        agents play the reference's DividedHardcodedAgent rules inside the env kernel in every rollout round (as in
+        evaluate(hardcoded_agents=...)), the action rings receive what they played, and they never train: no
+        sub-unit of theirs is drawn for an update, and under ``local`` / ``divided`` their nets' groups are frozen
+        (weights, policy_old and Adam moments keep their bits; their loss entries are NaN). None (the default)
+        changes nothing; an empty list is a trainer without the argument, bit for bit. ValueError under free
+        prices, for an index outside [0, N) and for a mask that leaves no agent to train."""
         assert arch in ("divided", "local", "global")
         self.fused = fused  # fused HIP gradient (ms_ppo_grad) vs torch autograd
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
@@ -183,6 +190,23 @@ class Trainer:
         N, C, L = s.n_agents, s.n_cores, s.collection_length
         self.N, self.C, self.L = N, C, L
         self.free = bool(cfg.free_prices)
+        self.hardcoded = None
+        if hardcoded_agents is not None:  # evaluate()'s checks, and somebody must be left to train
+            if self.free:
+                raise ValueError("the hard-coded agents act under fixed prices only")
+            given = list(hardcoded_agents)
+            if any(isinstance(a, bool) or not isinstance(a, (int, np.integer, float, np.floating)) or a != int(a)
+                   for a in given) or any(not 0 <= int(a) < N for a in given):
+                raise ValueError("hardcoded_agents must be agent indices in [0, %d)" % N)
+            self.hardcoded = sorted({int(a) for a in given})
+            if len(self.hardcoded) == N:
+                raise ValueError("hardcoded_agents covers every agent: nothing would train")
+            if self.hardcoded and arch != "global" and not fused:
+                raise ValueError("frozen groups (hardcoded_agents under 'local' / 'divided') need the fused update")
+        self.hc_mask = sum(1 << a for a in self.hardcoded or [])
+        self.learned = [a for a in range(N) if not (self.hc_mask >> a) & 1]
+        # hardcoded_agents=[]: the fused launches go through the mixed library calls with mask 0 (the plain kernels)
+        self._empty_mask = 0 if self.hardcoded == [] else None
         T = self.T = self.hp.update_step
         hp = self.hp
         max_len = max(cfg.job_length[: cfg.n_kinds])
@@ -221,6 +245,14 @@ class Trainer:
             self.price = _Unit("price", self.E, T, N * L, (N * L) // go, 4, 4, s.price_actions,
                                mk(go, 4, s.price_actions, hp.offer_gamma, k_off, nets["price"]), dev, torch.float32,
                                unit_major=self.price_unit_major)
+        # the masked agents' groups never step (HipAdam.freeze); global: the one shared net trains on the others
+        self._frozen = {}
+        if self.hc_mask and arch != "global":
+            for u, per_agent in ((self.acc, C), (self.off, L)):
+                G = u.group.policy.G
+                flags = [bool((self.hc_mask >> ((g * u.S) // per_agent)) & 1) for g in range(G)]
+                u.group.hip_optimizer.freeze(flags, G)
+                self._frozen[u.name] = torch.tensor([g for g in range(G) if flags[g]], dtype=torch.long, device=dev)
         if world_size > 1:
             self._broadcast_params()
         # A single net's item i takes word (i >> 6) & 1 of the draw countered by item i & ~64 (k_act_common's rule on
@@ -303,6 +335,9 @@ class Trainer:
                            self.off.group.policy.G == 1 and self.T > 1 and
                            os.environ.get("MS_ENV_FUSED_ACT", "1") != "0" and fused_metrics_ok and
                            all(env.fused_act_supported() for env, _, _ in self.env.parts))
+        # a mixed market: the fused launches' mixed forms (ABI 24), else an act launch and step_mixed per round
+        if self.hc_mask and not all(env.fused_mixed_supported() for env, _, _ in self.env.parts):
+            self.fused_step = False
         # ... and the whole rollout's rounds are one launch (ms_env_rollout_act): each wave steps and acts
         # for its replicas round after round (MS_ENV_ROLLOUT=0: one launch per round, for A/B measurements)
         self.fused_rollout = self.fused_step and os.environ.get("MS_ENV_ROLLOUT", "1") != "0"
@@ -478,9 +513,17 @@ class Trainer:
         if self.metric_bufs is not None:
             ev = dict(ev or {}, metrics=self.metric_bufs[k])
         nxt = self._fused_next(t + 1, k) if self.fused_step and t + 1 < self.T else None
+        if self.hc_mask:  # a mixed market: the ring slot receives what the masked agents played
+            acc_t, off_t = sl(self.acc.actions[t]).view(E, N, C), sl(self.off.actions[t]).view(E, N, L)
+            if nxt is not None:
+                env.step(acc_t, off_t, obs=obs, rewards=rew, events=ev, stream=st, next_act=nxt, hardcoded=self.hc_mask)
+            else:
+                env.step_mixed(acc_t, off_t, self.hc_mask, obs=obs, rewards=rew, events=ev, stream=st,
+                               taken=dict(acceptor=acc_t, offer_core=off_t))
+            return
         env.step(sl(self.acc.actions[t]).view(E, N, C), sl(self.off.actions[t]).view(E, N, L),
                  sl(self.env_price).view(E, N, L) if self.free else None, obs=obs, rewards=rew, events=ev, stream=st,
-                 next_act=nxt)
+                 next_act=nxt, hardcoded=self._empty_mask)
 
     def _fused_next(self, t: int, k: int):
         """Round t's getActionForAllAgents (the fixed-price pair of _act_part) for replica part k, as the
@@ -513,7 +556,7 @@ class Trainer:
                                      b(self.acc.logprobs), 8)
         env.rollout_act(sl(self.acc.actions[0]).view(E, N, C), sl(self.off.actions[0]).view(E, N, L), obs, rew,
                         self._fused_next(1, k), strides, self.T, act_after_last=False, events=ev,
-                        stream=self.streams[k])
+                        stream=self.streams[k], hardcoded=self.hc_mask or self._empty_mask)
 
     def _fused_next_free(self, t: int, k: int):
         """Round t's acting of a locally shared free-price round (act_round_free of _act_part) for replica part k,
@@ -688,6 +731,12 @@ class Trainer:
             acc = [[0] * N for _ in range(CS)]
             off = [[0] * N for _ in range(CS)]
             for a in range(N):  # per agent: acceptor draws then offer draws (Agent.py:716-728)
+                if (self.hc_mask >> a) & 1:
+                    # a rule-based agent draws nothing; its frozen group's gradient runs on its first sub-unit
+                    # and is discarded by the Adam step
+                    for i in range(CS):
+                        acc[i][a], off[i][a] = a * C, a * L
+                    continue
                 for i in range(CS):
                     acc[i][a] = a * C + self.rng.randint(0, C - 1)
                 for j in range(CS):
@@ -696,12 +745,15 @@ class Trainer:
                        offer=[torch.tensor(r, device=dev) for r in off])
         else:
             acc, off = [], []
+            # a mixed market: the agent is drawn among the learned ones (their rows alone hold sampled actions)
+            agent = (lambda: self.learned[self.rng.randint(0, len(self.learned) - 1)]) if self.hc_mask else \
+                (lambda: self.rng.randint(0, N - 1))
             for _ in range(CS):  # SchedulingEnvironment.py:315-321
-                a = self.rng.randint(0, N - 1)
+                a = agent()
                 c = self.rng.randint(0, C - 1)
                 acc.append(torch.tensor([a * C + c], device=dev))
             for _ in range(CS):  # SchedulingEnvironment.py:323-329
-                a = self.rng.randint(0, N - 1)
+                a = agent()
                 l = self.rng.randint(0, L - 1)
                 off.append(torch.tensor([a * L + l], device=dev))
             sel = dict(acceptor=acc, offer=off)
@@ -841,7 +893,7 @@ class Trainer:
             for u, _, _ in live:
                 u.group.hip_optimizer.step()
         for u, _, ls in steps.values():
-            losses[u.name] = combine_losses(terms[u.name])
+            losses[u.name] = self._mask_losses(u, combine_losses(terms[u.name]))
             u.group.last_losses = list(losses[u.name].unbind(0))
             u.group.sync_old()
         self._carry_last_observation()
@@ -884,13 +936,19 @@ class Trainer:
                 for i, ep in enumerate(seq):
                     ep.launch(terms[i])
                     u.group.hip_optimizer.step(st)
-                losses[u.name] = combine_losses(terms)
+                losses[u.name] = self._mask_losses(u, combine_losses(terms))
                 u.group.last_losses = list(losses[u.name].unbind(0))
                 u.group.sync_old()
         for st in self._unit_streams:
             cur.wait_stream(st)
         self._carry_last_observation()
         return losses
+
+    def _mask_losses(self, u, losses):
+        """The frozen groups' entries of a unit type's [n][G] losses as NaN: their gradient ran on rows the rules
+        played and was discarded."""
+        idx = self._frozen.get(u.name)
+        return losses if idx is None else losses.index_fill_(1, idx, float("nan"))
 
     def _torch_update(self, sel):
         """The torch-autograd update (the numerical reference of the fused one)."""
@@ -942,8 +1000,11 @@ class Trainer:
             raw = torch.cat([b[slot] for b in self.metric_bufs]).cpu().numpy()
             for b in self.metric_bufs:
                 b[slot].zero_()
-            self.episode_log.append(mx.episode_values(mx.view(raw), self.cfg, self.ep_len, s.n_agents, s.n_cores,
-                                                      s.collection_length))
+            ep = mx.episode_values(mx.view(raw), self.cfg, self.ep_len, s.n_agents, s.n_cores, s.collection_length)
+            if self.hardcoded is not None:  # what each side earns (evaluate()'s split), per replica
+                for d in ep:
+                    d["agentRew_hardcoded"], d["agentRew_learned"] = mx.split_agent_rew(d["agentRew"], self.hardcoded)
+            self.episode_log.append(ep)
 
     # ---- evaluation
     def eval_seed(self, n_envs: int | None = None) -> int:
@@ -1107,10 +1168,8 @@ class Trainer:
                    per_replica=per_replica)
         if mixed:
             res["hardcoded_agents"] = hc
-            rest = [a for a in range(N) if a not in hc]
             for ep in res["episodes"]:
-                ep["agentRew_hardcoded"] = float(np.mean(ep["agentRew"][hc])) if hc else None
-                ep["agentRew_learned"] = float(np.mean(ep["agentRew"][rest])) if rest else None
+                ep["agentRew_hardcoded"], ep["agentRew_learned"] = mx.split_agent_rew(ep["agentRew"], hc)
         if trace:
             res["trace"] = rounds
         return res

@@ -1,0 +1,451 @@
+"""Training in a mixed market: Trainer(hardcoded_agents=[...]) puts rule-based agents into the PPO rollouts by
+mask (ms_env_step_act_mixed / ms_env_rollout_act_mixed, or an act launch and ms_env_step_mixed per round), keeps
+them out of the update (no draws, frozen groups through ms_adam_step_dev_masked) and saves the mask with the run.
+Everything is compared bit for bit: the one-launch rollout against the launch pairs, the played trajectory against
+the object-faithful restatement (oracle/pyref.py), graph against eager, a resumed run against the uninterrupted one.
+
+Which kernel a case reaches (env_kernels.hip lanes_per_env): below 1024 replicas every shape here steps with 16
+lanes per replica, i.e. the <16, DynShape> kernels, 4x4x3 included; the FixShape<4, 4, 3, 1> kernels run 4x4x3 from
+2049 to 4096 replicas (32 lanes), the <64, DynShape> ones from 1024 to 2048, the <32, DynShape> ones another shape
+from 2049 replicas. 6x5x2 at 40 replicas is outside the fused kernels' range (4 replicas a wave, 120 acceptor
+items), so every one of its trainers steps with launch pairs. DISPATCH adds one case per remaining kernel."""
+import contextlib
+import ctypes as ct
+import importlib
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import pyref
+from tests.drivers import compare_state
+from tests.test_hardcoded_gpu import _pcfg, _pyref_export
+from tests.test_mixed_gpu import masked_hardcoded_actions
+
+pytestmark = pytest.mark.gpu
+
+SEED, T = 3, 6
+# six job kinds of unequal reward ratio, so that the acceptor rule finds better offers within a few rounds (two
+# kinds of equal priority / length ratio never do within T = 6: measured 0 accepted offers in 40 replicas)
+_JOBS = dict(priorities=[2, 4, 6, 8, 10, 12], lengths=[5] * 6, fix_prices=[1, 3, 5, 7, 9, 11],
+             probabilities=[0.25, 0.25, 0.125, 0.125, 0.125, 0.125])
+SHAPE_KW = {"4x4x3": None, "6x5x2": dict(n_agents=6, n_cores=5, collection_length=2, **_JOBS)}
+SHAPES = [("4x4x3", 96), ("4x4x3", 33), ("6x5x2", 40)]
+# one case per fused kernel the shapes above do not reach: (shape, E, kernel)
+DISPATCH = [("4x4x3", 2065, "32 lanes, FixShape<4,4,3,1>, last wave half filled"), ("4x4x3", 1025, "64 lanes, DynShape"),
+            ("6x5x2", 2051, "32 lanes, DynShape, last wave half filled")]
+PAIRS = (dict(MS_ENV_ROLLOUT="0"), dict(MS_ENV_FUSED_ACT="0"))
+
+
+def _masks(N):
+    return [[0], [N - 1], [1, 2], [a for a in range(N) if a != 1], []]
+
+
+def _mod(name):
+    return importlib.import_module("marl-scheduling_amd." + name)
+
+
+def _cfg(shape):
+    abi = _mod("abi")
+    kw = SHAPE_KW[shape]
+    return abi.named_config("cfg2") if kw is None else abi.make_config(**kw)
+
+
+@contextlib.contextmanager
+def _environ(env):
+    old = {k: os.environ.get(k) for k in env}
+    os.environ.update(env)
+    try:
+        yield
+    finally:
+        for k, v in old.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+
+
+def _trainer(shape, E, mask, arch="global", env=None, t=T, **kw):
+    """A trainer of the shape; env: the environment its constructor reads (the rollout path knobs)."""
+    tr = _mod("trainer")
+    kw.setdefault("use_graph", False)
+    with _environ(env or {}):
+        return tr.Trainer(_cfg(shape), E, arch=arch, hyper=tr.Hyper(update_step=t), seed=SEED, device="cuda:0",
+                          hardcoded_agents=mask, **kw)
+
+
+def _units_of(t, mask):
+    """(acceptor units, offer units) of the masked agents, as index tensors."""
+    dev = t.device
+    acc = [a * t.C + c for a in mask for c in range(t.C)]
+    off = [a * t.L + s for a in mask for s in range(t.L)]
+    return torch.tensor(acc, dtype=torch.long, device=dev), torch.tensor(off, dtype=torch.long, device=dev)
+
+
+def _state(t, losses, mask=()):
+    """Everything a run leaves behind; the masked units' log-probs (they belong to no played action) are left out."""
+    st = {}
+    for i, ls in enumerate(losses):
+        for k, v in ls.items():
+            st["loss%d.%s" % (i, k)] = v.clone()
+    ua, uo = _units_of(t, list(mask))
+    for u, masked in ((t.acc, ua), (t.off, uo)):
+        g = u.group
+        for pol_name, pol in (("policy", g.policy), ("policy_old", g.policy_old)):
+            for k, p in pol.named_parameters():
+                st["%s.%s.%s" % (u.name, pol_name, k)] = p.detach().clone()
+        if t.fused:
+            opt = g.hip_optimizer
+            for i, p in enumerate(q for grp in opt.param_groups for q in grp["params"]):
+                st["%s.adam%d.m" % (u.name, i)] = opt.state[p]["exp_avg"].clone()
+                st["%s.adam%d.v" % (u.name, i)] = opt.state[p]["exp_avg_sq"].clone()
+            st[u.name + ".adam.step"] = int(opt.step_dev)
+        st[u.name + ".actions"] = u.actions.clone()
+        st[u.name + ".logprobs"] = u.logprobs.clone().index_fill_(2, masked, 0.0)
+        st[u.name + ".rewards"] = u.rewards.clone()
+    st["off_obs"], st["acc_rows"], st["acc_owner"] = t.off_obs.clone(), t.acc_rows.clone(), t.acc_owner.clone()
+    st["agent_reward"], st["auct_reward"] = t.agent_reward.clone(), t.auct_reward.clone()
+    st["env"] = [env.export_state() for env, _, _ in t.env.parts]  # (MT words and flags included)
+    st["counters"] = (t.rounds_done, t.rng.getstate(), int(t.rng_ctr), t.flags(), t.env.round)
+    return st
+
+
+def _assert_same(a, b, what=""):
+    if isinstance(a, dict):
+        assert a.keys() == b.keys(), what
+        for k in a:
+            _assert_same(a[k], b[k], "%s.%s" % (what, k))
+    elif isinstance(a, (list, tuple)):
+        assert len(a) == len(b), what
+        for i, (x, y) in enumerate(zip(a, b)):
+            _assert_same(x, y, "%s[%d]" % (what, i))
+    elif isinstance(a, torch.Tensor):
+        assert torch.equal(a, b) or (a.is_floating_point() and torch.equal(a.isnan(), b.isnan()) and
+                                     torch.equal(a.nan_to_num(0.0), b.nan_to_num(0.0))), what
+    elif isinstance(a, np.ndarray):
+        assert np.array_equal(a, b), what
+    else:
+        assert a == b, what
+
+
+def _poison_logprobs(t, mask):
+    ua, uo = _units_of(t, mask)
+    t.acc.logprobs_raw.index_fill_(2, ua, float("nan"))
+    t.off.logprobs_raw.index_fill_(2, uo, float("nan"))
+
+
+def _poison_rows(t, mask):
+    """The masked agents' ring rows as nothing may read them: other (valid) actions, NaN log-probs, huge rewards,
+    0x55 offer observations."""
+    ua, uo = _units_of(t, mask)
+    _poison_logprobs(t, mask)
+    for u, idx in ((t.acc, ua), (t.off, uo)):
+        a = u.actions_raw.index_select(2, idx)
+        u.actions_raw.index_copy_(2, idx, ((a + 1) % u.group.policy.A).to(torch.int8))
+        u.rewards.index_fill_(2, idx, 1 << 20)
+    t.off_obs[: t.T].index_fill_(2, uo, 0x55)
+
+
+def _run(t, n, mask=(), poison=None):
+    """n iterations as rollout + update, poison(t, mask) between the two."""
+    losses = []
+    for _ in range(n):
+        t.rollout()
+        if poison is not None and mask:
+            poison(t, list(mask))
+        losses.append(t.update())
+    return _state(t, losses, mask)
+
+
+# ---- 1. one launch equals the launch pairs
+
+def _one_launch_case(shape, E, mask, t=T):
+    a = _trainer(shape, E, mask, t=t)
+    want = _run(a, 2, mask, _poison_logprobs)  # nothing reads the masked units' log-probs
+    for env in PAIRS:
+        b = _trainer(shape, E, mask, env=env, t=t)
+        assert not b.fused_rollout and (env.get("MS_ENV_FUSED_ACT") != "0" or not b.fused_step)
+        _assert_same(_run(b, 2, mask), want, "%s E=%d %r %r" % (shape, E, mask, env))
+    assert a.flags() == 0
+    return a
+
+
+@pytest.mark.parametrize("mask_i", range(5), ids=["first", "last", "pair", "all-but-one", "empty"])
+@pytest.mark.parametrize("shape,E", SHAPES, ids=["%s-%d" % s for s in SHAPES])
+def test_one_launch_equals_pairs(ms, shape, E, mask_i):
+    """Two iterations (the update between them) of arch global as one launch per rollout, as one launch per round
+    (MS_ENV_ROLLOUT=0) and as an act launch and a mixed env launch per round (MS_ENV_FUSED_ACT=0): every ring,
+    agent_reward, the losses, the nets and Adam, the exported env state (MT words, flags) are equal. The masked
+    units' log-probs are left out and, in the one-launch run, NaN before each update."""
+    a = _one_launch_case(shape, E, _masks(_cfg(shape).n_agents)[mask_i])
+    assert a.fused_rollout == (shape == "4x4x3")
+
+
+@pytest.mark.parametrize("shape,E,kernel", DISPATCH, ids=[d[2].split(",")[0] + "-" + d[0] for d in DISPATCH])
+def test_one_launch_equals_pairs_wide_groups(ms, shape, E, kernel):
+    """The same at the replica counts that reach the kernels of 32 and 64 lanes per replica (T 4, mask {1, 2})."""
+    a = _one_launch_case(shape, E, [1, 2], t=4)
+    assert a.fused_rollout, kernel
+
+
+def test_t1_has_no_fused_acting(ms):
+    """T 1: no ring slot to act into, so every trainer steps with launch pairs; the paths still agree."""
+    a = _one_launch_case("4x4x3", 33, [0], t=1)
+    assert not a.fused_step
+
+
+# ---- 2. the played trajectory is the rules'
+
+@pytest.mark.parametrize("mask_i", range(4), ids=["first", "last", "pair", "all-but-one"])
+@pytest.mark.parametrize("shape,E", SHAPES, ids=["%s-%d" % s for s in SHAPES])
+def test_played_trajectory_is_the_rules(ms, shape, E, mask_i):
+    """One rollout's action rings replayed on the restatement and, with the rules' tie-break draws made first by
+    ms_env_randbelow, through ms_env_step on a fresh env: the masked agents' ring rows are the restatement's picks,
+    observations, rewards and the final state (MT words included) are the restatement's and the replayed env's.
+    The market is not degenerate: over the T = 6 rounds of all replicas the masked agents of the cases (4x4x3-96,
+    4x4x3-33, 6x5x2-40; masks first, last, pair, all-but-one) took
+      non-reject acceptor actions 33 32 44 68 | 9 11 12 20 | 13 13 24 53
+      and placed offers           520 535 1046 1611 | 182 180 357 547 | 144 145 308 765
+    on the restatement alone (this test's own counters, printed before the assertion); both are asserted >= 1.
+    The seed and the job kinds were chosen on the CPU, with the restatement and random learned agents."""
+    abi = ms.abi
+    cfg, kw = _cfg(shape), SHAPE_KW[shape]
+    mask = _masks(cfg.n_agents)[mask_i]
+    bits = sum(1 << a for a in mask)
+    tr = _trainer(shape, E, mask)
+    tr.rollout()
+    N, C, L, dev = tr.N, tr.C, tr.L, tr.device
+    base = _mod("trainer").env_seed(SEED, 0, E)
+    worlds = [pyref.PyWorld(_pcfg(abi, cfg, kw), base + e) for e in range(E)]
+    draws = []
+    for w in worlds:
+        w.rng.sample = lambda pop, k, _sample=w.rng.sample: (draws.append(len(pop)), _sample(pop, k))[1]
+    env = ms.BatchedEnv(cfg, E, seed=base)
+    obs = env.compact_obs_buffers()
+    env.reset(obs)
+    aa, ao = tr.acc.actions.cpu().numpy(), tr.off.actions.cpu().numpy()
+    ra, ro = tr.acc.rewards.cpu().numpy(), tr.off.rewards
+    nonreject = offers = 0
+    for t in range(T):
+        for e, w in enumerate(worlds):
+            acc, off = aa[t, e].reshape(N, C).astype(int), ao[t, e].reshape(N, L).astype(int)
+            rule_acc, rule_off = acc.copy(), off.copy()
+            rule_acc[mask], rule_off[mask] = -1, -1
+            del draws[:]
+            masked_hardcoded_actions(w, bits, rule_acc, rule_off)
+            assert np.array_equal(rule_acc, acc) and np.array_equal(rule_off, off), (t, e)
+            for n in draws:
+                env.randbelow(n, e)
+            nonreject += int((acc[mask] != w.O).sum())
+        _, rew, _ = env.step(tr.acc.actions[t].view(E, N, C), tr.off.actions[t].view(E, N, L), obs=obs)
+        for e, w in enumerate(worlds):
+            _, r, _, _ = w.step(aa[t, e].reshape(N, C).tolist(), ao[t, e].reshape(N, L).tolist())
+            offers += sum(1 for o in w.offers if o.offerer - 1 in mask)
+            np.testing.assert_array_equal(ra[t, e].reshape(N, C), r[1][..., 0], err_msg="t=%d e=%d" % (t, e))
+            if t == T - 1:
+                np.testing.assert_array_equal(tr.agent_reward[e].cpu().numpy(), r[3])
+        for k, ring in (("offer", tr.off_obs), ("core_rows", tr.acc_rows), ("core_owner", tr.acc_owner)):
+            assert torch.equal(obs[k].reshape(ring[t + 1].shape), ring[t + 1]), (k, t)
+        assert torch.equal(rew["offer"].view(E, N * L), ro[t]) and torch.equal(rew["acceptor"].view(E, N * C), tr.acc.rewards[t])
+    print("counts %s E=%d mask=%r: nonreject=%d offers=%d" % (shape, E, mask, nonreject, offers))
+    got = tr.env.parts[0][0].export_state()
+    compare_state(got, [_pyref_export(w) for w in worlds], E)
+    _assert_same(env.export_state(), got)
+    assert tr.flags() == 0 and env.flags() == 0
+    assert nonreject >= 1 and offers >= 1, (nonreject, offers)
+
+
+# ---- 3. the empty mask is the unmasked trainer
+
+@pytest.mark.parametrize("env", [{}, dict(MS_ENV_ROLLOUT="0"), dict(MS_ENV_FUSED_ACT="0")], ids=["one-launch", "per-round", "pairs"])
+def test_empty_mask_is_unmasked(ms, env):
+    want = _run(_trainer("4x4x3", 33, None, env=env), 2)
+    _assert_same(_run(_trainer("4x4x3", 33, [], env=env), 2), want)
+
+
+class _Spy:
+    """A library entry point that records the masks it is called with."""
+
+    def __init__(self, fn, mask_arg):
+        self.fn, self.mask_arg, self.masks = fn, mask_arg, []
+        self.argtypes, self.restype = fn.argtypes, fn.restype
+
+    def __call__(self, *args):
+        self.masks.append(int(args[self.mask_arg]))
+        return self.fn(*args)
+
+
+def test_mask_zero_through_the_new_calls(ms, monkeypatch):
+    """hardcoded_agents=[] steps through ms_env_rollout_act_mixed / ms_env_step_act_mixed with mask 0 (seen by a
+    spy on the library object), which equals the old calls bit for bit."""
+    lib = ms._lib.lib
+    roll, step = _Spy(lib.ms_env_rollout_act_mixed, 9), _Spy(lib.ms_env_step_act_mixed, 6)
+    monkeypatch.setattr(lib, "ms_env_rollout_act_mixed", roll)
+    monkeypatch.setattr(lib, "ms_env_step_act_mixed", step)
+    for env, spy, calls in (({}, roll, 2), (dict(MS_ENV_ROLLOUT="0"), step, 2 * (T - 1))):
+        want = _run(_trainer("4x4x3", 96, None, env=env), 2)
+        assert spy.masks == []
+        _assert_same(_run(_trainer("4x4x3", 96, [], env=env), 2), want)
+        assert spy.masks == [0] * calls
+
+
+# ---- 5. the update ignores the masked agents' rows (global)
+
+def test_update_ignores_masked_rows(ms):
+    want = _run(_trainer("4x4x3", 96, [1, 2]), 2)
+    got = _run(_trainer("4x4x3", 96, [1, 2]), 2, [1, 2], _poison_rows)
+    keys = [k for k in want if k.startswith("loss") or ".policy" in k or ".adam" in k]
+    assert len(keys) > 20
+    for k in keys:
+        _assert_same(got[k], want[k], k)
+
+
+# ---- 6. frozen groups (local, divided)
+
+def _adam_tensors(t):
+    out = {}
+    for u in (t.acc, t.off):
+        opt = u.group.hip_optimizer
+        for i, p in enumerate(q for grp in opt.param_groups for q in grp["params"]):
+            out["%s.%d" % (u.name, i)] = (u, p, opt.state[p]["exp_avg"], opt.state[p]["exp_avg_sq"])
+    return out
+
+
+@pytest.mark.parametrize("arch", ["local", "divided"])
+def test_frozen_groups(ms, arch):
+    """The masked agents' groups start with non-zero Adam moments; after two iterations their weights, policy_old
+    and moments have the bits they had, their losses are NaN, and the learned groups' weights and losses are those
+    of a run whose masked rows were poisoned (NaN log-probs, huge rewards: the frozen groups' gradient is NaN)."""
+    mask, E = [1, 2], 32
+    runs = []
+    for poison in (None, _poison_rows):
+        t = _trainer("4x4x3", E, mask, arch=arch)
+        frozen = {u.name: t._frozen[u.name] for u in (t.acc, t.off)}
+        G = {u.name: u.group.policy.G for u in (t.acc, t.off)}
+        assert {k: v.numel() for k, v in frozen.items()} == (dict(acceptor=2, offer=2) if arch == "local" else
+                                                               dict(acceptor=2 * t.C, offer=2 * t.L))
+        with torch.no_grad():
+            for u, p, m, v in _adam_tensors(t).values():
+                m[frozen[u.name]] = 0.25
+                v[frozen[u.name]] = 0.5
+        before = {}
+        for k, (u, p, m, v) in _adam_tensors(t).items():
+            before[k] = [x.detach()[frozen[u.name]].clone() for x in (p, m, v)]
+        old_before = {u.name: {k: p.detach()[frozen[u.name]].clone() for k, p in u.group.policy_old.named_parameters()}
+                      for u in (t.acc, t.off)}
+        st = _run(t, 2, mask, poison)
+        for k, (u, p, m, v) in _adam_tensors(t).items():
+            for x, b in zip((p, m, v), before[k]):
+                assert torch.equal(x.detach()[frozen[u.name]], b), (arch, k)
+        for u in (t.acc, t.off):
+            for k, p in u.group.policy_old.named_parameters():
+                assert torch.equal(p.detach()[frozen[u.name]], old_before[u.name][k]), (arch, u.name, k)
+        learned = {n: torch.tensor([g for g in range(G[n]) if g not in set(frozen[n].tolist())], device=t.device)
+                   for n in G}
+        keep = {}
+        for k, v in st.items():
+            name = k.split(".")[1] if k.startswith("loss") else k.split(".")[0]
+            if k.startswith("loss"):
+                assert v[:, frozen[name]].isnan().all() and not v[:, learned[name]].isnan().any(), k
+                keep[k] = v[:, learned[name]]
+            elif ".policy" in k or (".adam" in k and not k.endswith("step")):
+                keep[k] = v[learned[name]]
+        assert t.flags() == 0 and len(keep) > 20
+        runs.append(keep)
+    _assert_same(runs[1], runs[0], arch)
+
+
+# ---- 7. graph equals eager
+
+def test_graph_equals_eager(ms):
+    states = []
+    for use_graph in (True, False):
+        t = _trainer("4x4x3", 96, [0], use_graph=use_graph)
+        states.append(_state(t, [t.iteration() for _ in range(3)], [0]))
+    _assert_same(states[0], states[1])
+
+
+# ---- 8. argument checks
+
+def test_argument_checks(ms):
+    abi, lib, tr = ms.abi, ms._lib.lib, _mod("trainer")
+    with pytest.raises(ValueError):
+        tr.Trainer.from_named("cfg3", n_envs=16, update_step=4, device="cuda:0", hardcoded_agents=[0])
+    for bad in ([4], [-1], [0, 1, 2, 3], [0.5], ["1"]):
+        with pytest.raises(ValueError):
+            _trainer("4x4x3", 16, bad)
+    with pytest.raises(ValueError):
+        _trainer("4x4x3", 16, [0], arch="local", fused=False)
+    assert _trainer("4x4x3", 16, [2, 0, 2, 1.0]).hardcoded == [0, 1, 2]
+    # the C calls: MS_EINVAL (22) with a message, nothing launched
+    for name, mask in (("cfg3", 1), ("cfg2", 1 << 4)):
+        env = ms.BatchedEnv(abi.named_config(name), 8, seed=1)
+        acc = torch.full((8, env.N, env.C), env.O, dtype=torch.int8, device=env.device)
+        off = torch.zeros((8, env.N, env.L), dtype=torch.int8, device=env.device)
+        a = abi.MsActions(ms._lib.ptr(acc), ms._lib.ptr(off), ms._lib.ptr(off) if env.free_prices else None, None)
+        nxt, strides = abi.MsFusedAct(), abi.MsRoundStrides()
+        rc = lib.ms_env_step_act_mixed(env._h, ct.byref(a), None, None, None, ct.byref(nxt), mask, ms._lib.stream_ptr())
+        assert rc == abi.EINVAL == 22 and b"ms_env_step_act_mixed" in lib.ms_last_error()
+        rc = lib.ms_env_rollout_act_mixed(env._h, ct.byref(a), None, None, None, ct.byref(nxt), ct.byref(strides), 2, 0,
+                                          mask, ms._lib.stream_ptr())
+        assert rc == 22 and b"ms_env_rollout_act_mixed" in lib.ms_last_error()
+        assert env.round == 0 and env.flags() == 0
+
+
+# ---- 9. checkpoints
+
+def test_checkpoint(ms, tmp_path):
+    ck = _mod("checkpoint")
+    mk = lambda mask: _trainer("4x4x3", 33, mask, use_graph=True)
+    whole = mk([0])
+    want = _state(whole, [whole.iteration(), whole.iteration()], [0])
+    first = mk([0])
+    l1 = first.iteration()
+    path = str(tmp_path / "mixed.ckpt")
+    first.save_checkpoint(path)
+    assert ck.read_file(path)[0]["hardcoded_agents"] == [0]
+    resumed = mk([0])
+    resumed.load_checkpoint(path)
+    got = _state(resumed, [l1, resumed.iteration()], [0])
+    _assert_same(got, want)
+    for other in ([1], None, []):
+        with pytest.raises(ValueError, match="hardcoded_agents"):
+            mk(other).load_checkpoint(path)
+    mk(None).load_policy(path)  # the nets alone: the mask is not looked at
+    # a file of the format before the field: written by an unmasked trainer, the field stripped
+    plain = mk(None)
+    p1 = plain.iteration()
+    old = str(tmp_path / "old.ckpt")
+    plain.save_checkpoint(old)
+    manifest, state = ck.read_file(old)
+    manifest.pop("hardcoded_agents", None)
+    assert "hardcoded_agents" not in manifest
+    ck.write_file(old, manifest, state)
+    again = mk([])
+    again.load_checkpoint(old)
+    _assert_same(_state(again, [p1, again.iteration()]), _state(plain, [p1, plain.iteration()]))
+    with pytest.raises(ValueError, match="hardcoded_agents"):
+        mk([0]).load_checkpoint(old)
+
+
+# ---- 10. metrics
+
+def test_metrics_split(ms):
+    """metrics=True: every harvested episode carries the split of its agentRew, per replica, on both rollout paths
+    (the mixed kernels' metrics forms against ms_env_step_mixed's), which also agree on every other value."""
+    mask, logs = [0, 3], []
+    for env in ({}, dict(MS_ENV_FUSED_ACT="0")):
+        t = _trainer("4x4x3", 33, mask, env=env, metrics=True, episode_length=3)
+        t.iteration()
+        assert len(t.episode_log) == 2 and t.fused_rollout == (not env)
+        for ep in t.episode_log:
+            assert len(ep) == 33
+            for d in ep:
+                assert d["agentRew_hardcoded"] == float(np.mean(d["agentRew"][mask]))
+                assert d["agentRew_learned"] == float(np.mean(d["agentRew"][[1, 2]]))
+        logs.append(t.episode_log)
+    _assert_same(logs[0], logs[1])
+    plain = _trainer("4x4x3", 33, None, metrics=True, episode_length=3)
+    plain.iteration()
+    assert "agentRew_hardcoded" not in plain.episode_log[0][0]
