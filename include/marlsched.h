@@ -626,7 +626,13 @@ int ms_discounted_returns(const float* rewards, int32_t T, int64_t M, int64_t ro
  * reward buffer: rewards [T][E][U] (f32, or int32 with rewards_i32 = 1), sequence (e, g) is
  * unit unit_of_group[g] of replica e; out [T][E][G] f32 (the ms_ppo_batch.returns layout).
  * unit_of_group may list the sub-units of several update draws (Agent.py:716-728) back to back:
- * draw d then reads returns + d*G_draw with returns_ld = G. */
+ * draw d then reads returns + d*G_draw with returns_ld = G.
+ * Magnitude contract: |reward| <= 2^22 (4194304). The std comes from one pass's float64 sums as
+ * ss - 2*mean*s + T*mean^2, which is exact enough only while the sums of squares add without rounding; up to
+ * 2^22 the outputs stay within the f32 bound of a float64 evaluation at every gamma in [0, 1], at 2^23 a
+ * sequence of large offset and small variance comes out with a std of 0 (tests/test_update_ref.py). The env
+ * emits reward_multiplier * priority, small integers. ms_discounted_returns (two passes) has no such limit.
+ * T == 1 gives NaN (the unbiased std of one sample), an all-zero sequence exact zeros. */
 int ms_unit_returns(const void* rewards, int32_t rewards_i32, int32_t T, int64_t E, int32_t U,
                     const int32_t* unit_of_group, int32_t G, double gamma, float* out, void* stream);
 

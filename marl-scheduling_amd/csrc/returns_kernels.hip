@@ -77,7 +77,9 @@ __global__ void __launch_bounds__(256) k_unit_returns(const void* __restrict__ r
     }
     const float mean = (float)(s / T);
     // sum of squared deviations from the f32 mean, from the same pass's sums (no second read):
-    // sum (f - m)^2 = ss - 2 m s + T m^2 in double (the f32 inputs leave it well conditioned)
+    // sum (f - m)^2 = ss - 2 m s + T m^2 in double. Three terms of about T * reward^2 cancel: good while the
+    // squares add exactly, i.e. for |reward| <= 2^22 (the contract in marlsched.h; the env's rewards are small
+    // integers); at 2^23 a large offset under a small variance gives v = 0 (tests/test_update_ref.py)
     const double md = (double)mean;
     double v = ss - 2.0 * md * s + (double)T * md * md;
     v = v > 0.0 ? v : 0.0;

@@ -776,7 +776,7 @@ def test_trainer_two_stream_rollout(ms):
 
 
 def test_hip_adam_matches_torch_adam(ms):
-    """ms_adam_step (HipAdam) against torch.optim.Adam with the actor / critic param groups of
+    """ms_adam_step_dev (what HipAdam.step calls) against torch.optim.Adam with the actor / critic param groups of
     PPO.__init__ (PPOmodules.py:100-105), over several steps with changing gradients."""
     ppo = _ppo(ms)
     gen = torch.Generator().manual_seed(3)
