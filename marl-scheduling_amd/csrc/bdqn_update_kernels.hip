@@ -21,9 +21,12 @@
 //   k_bdqn_upd_w1      dW1 = d pre1^T x (bf16 MFMA: d pre1 as three exact bf16 terms, x exact), db1
 //
 // Every sum runs in a fixed order (MFMA accumulation is deterministic), so a replay reproduces the
-// gradient bit for bit. Products are exact f32 products, sums f32 as the reference's torch forward /
-// autograd; the summation orders differ from torch's GEMMs, so results agree within f32 rounding
-// (tests/test_bdqn_gpu.py against oracle/bdqn_ref.py and torch autograd).
+// gradient bit for bit. The sums over the rows that no MFMA takes (the four bias gradients and the loss)
+// accumulate in f64 and round once: a plain f32 running sum of 128 terms of both signs lost up to 16 eps
+// of the result (tests/test_learner_parity_gpu.py). Products are exact f32 products, the other sums f32
+// as the reference's torch forward / autograd; the summation orders differ from torch's GEMMs, so
+// results agree within f32 rounding (tests/test_bdqn_gpu.py against oracle/bdqn_ref.py and torch
+// autograd).
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -557,9 +560,9 @@ __global__ void __launch_bounds__(256) k_bdqn_upd_wgrad(BdqnUpd p) {
         }
     if (tid < 32) {
         const int r = r0 + tid;
-        float s = 0.f;
-        for (int b = 0; b < p.B; b++) s += ds[b * kWgDP + tid];
-        s = clampg(s, cl);
+        double sd = 0.0;  // up to 128 terms of both signs in row order: summed in f64, rounded once
+        for (int b = 0; b < p.B; b++) sd += (double)ds[b * kWgDP + tid];
+        const float s = clampg((float)sd, cl);
         if (l2)
             p.g.b2[r] = s;
         else if (r < Mn)
@@ -568,9 +571,9 @@ __global__ void __launch_bounds__(256) k_bdqn_upd_wgrad(BdqnUpd p) {
             p.g.bv[0] = s;
     }
     if (blockIdx.x == 0 && tid == 64) {
-        float l = 0.f;
-        for (int b = 0; b < p.B; b++) l += p.lossb[b];
-        p.g.loss[0] = l / (float)(p.B * p.q.ac_dim);
+        double l = 0.0;
+        for (int b = 0; b < p.B; b++) l += (double)p.lossb[b];
+        p.g.loss[0] = (float)(l / (double)(p.B * p.q.ac_dim));
     }
 }
 
@@ -661,9 +664,9 @@ __global__ void __launch_bounds__(256) k_bdqn_upd_w1(BdqnUpd p) {
                     p.g.w1[(size_t)(32 * w + 16 * ht + 4 * g + q) * D + k] = clampg(acc[ht][kt][q], cl);
         }
     if (blockIdx.x == 0 && tid < 128) {
-        float s = 0.f;
-        for (int b = 0; b < p.B; b++) s += dp[b * kW1DP + tid];
-        p.g.b1[tid] = clampg(s, cl);
+        double s = 0.0;
+        for (int b = 0; b < p.B; b++) s += (double)dp[b * kW1DP + tid];
+        p.g.b1[tid] = clampg((float)s, cl);
     }
 }
 

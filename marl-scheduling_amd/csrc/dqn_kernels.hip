@@ -230,9 +230,9 @@ __global__ void __launch_bounds__(256) k_dqn_grad(DqnGradArgs a) {
         out[o] = s;
     }
     for (int o = tid; o < kQH; o += 256) {  // db1
-        float s = 0.f;
-        for (int rr = 0; rr < nrow; rr++) s += s_dpre[rr * (kQH + 1) + o];
-        out[kQH * D + o] = s;
+        double s = 0.0;  // the unweighted sums over the rows (db1, db2, the loss) run in f64 and round once
+        for (int rr = 0; rr < nrow; rr++) s += (double)s_dpre[rr * (kQH + 1) + o];
+        out[kQH * D + o] = (float)s;
     }
     for (int o = tid; o < A * kQH; o += 256) {  // dW2[i][j] = sum_{r: a_r = i} gd_r * h_r[j]
         const int i = o / kQH, j = o - i * kQH;
@@ -242,15 +242,15 @@ __global__ void __launch_bounds__(256) k_dqn_grad(DqnGradArgs a) {
         out[kQH * D + kQH + o] = s;
     }
     for (int o = tid; o < A; o += 256) {  // db2
-        float s = 0.f;
+        double s = 0.0;
         for (int rr = 0; rr < nrow; rr++)
-            if (s_a[rr] == o) s += s_gd[rr];
-        out[kQH * D + kQH + A * kQH + o] = s;
+            if (s_a[rr] == o) s += (double)s_gd[rr];
+        out[kQH * D + kQH + A * kQH + o] = (float)s;
     }
     if (tid == 0) {
-        float s = 0.f;
-        for (int rr = 0; rr < nrow; rr++) s += s_loss[rr];
-        out[wfl] = s;
+        double s = 0.0;
+        for (int rr = 0; rr < nrow; rr++) s += (double)s_loss[rr];
+        out[wfl] = (float)s;
     }
 }
 
@@ -260,8 +260,9 @@ __global__ void __launch_bounds__(256) k_dqn_reduce(DqnReduceArgs a) {
     const int p = blockIdx.x * 256 + threadIdx.x;
     if (p >= a.P) return;
     const float* src = a.partials + (int64_t)g * a.nblk * a.P + p;
-    float s = 0.f;
-    for (int b = 0; b < a.nblk; b++) s += src[(int64_t)b * a.P];
+    double sd = 0.0;  // block order, f64: a group of a few hundred thousand rows has a thousand partials
+    for (int b = 0; b < a.nblk; b++) sd += (double)src[(int64_t)b * a.P];
+    float s = (float)sd;
     const int D = a.D, A = a.A;
     const int o_b1 = kQH * D, o_w2 = o_b1 + kQH, o_b2 = o_w2 + A * kQH, o_loss = o_b2 + A;
     if (p == o_loss) {
