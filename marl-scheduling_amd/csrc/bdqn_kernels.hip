@@ -39,44 +39,11 @@
 #include "../../include/marlsched.h"
 #include "ms_bdqn.h"
 #include "ms_common.h"
+#include "ms_mfma.h"
 
 namespace ms {
 
 namespace {
-
-typedef float f4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t u4v __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ f4 mfma4(float a, float b, f4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-__device__ __forceinline__ f4 mfma_bf16(const u4v& a, const u4v& b, f4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0,
-                                                   0);
-}
-__device__ __forceinline__ uint32_t pack_hi(float lo, float hi) {
-    return __builtin_amdgcn_perm(__float_as_uint(hi), __float_as_uint(lo), 0x07060302u);
-}
-__device__ __forceinline__ uint32_t pack_i(int a, int b) { return pack_hi((float)a, (float)b); }
-__device__ __forceinline__ float trunc_bf16(float x) { return __uint_as_float(__float_as_uint(x) & 0xffff0000u); }
-
-// eight f32 values as three exact bf16 terms (hi + mid + lo == v: each term keeps 8 significant bits)
-__device__ __forceinline__ void split8(const float (&v)[8], u4v& hi, u4v& mid, u4v& lo) {
-#pragma unroll
-    for (int t = 0; t < 4; t++) {
-        float h[2], m[2], l[2];
-#pragma unroll
-        for (int u = 0; u < 2; u++) {
-            const float x = v[2 * t + u];
-            h[u] = trunc_bf16(x);
-            const float r = x - h[u];
-            m[u] = trunc_bf16(r);
-            l[u] = r - m[u];
-        }
-        hi[t] = pack_hi(h[0], h[1]);
-        mid[t] = pack_hi(m[0], m[1]);
-        lo[t] = pack_hi(l[0], l[1]);
-    }
-}
 
 // the foreign acceptor row F (Agent.py:167-212): [0, -1, -1, (-2, -2) * O]; zero past D
 __device__ __forceinline__ int foreign(int k, int D) { return k == 0 ? 0 : (k <= 2 ? -1 : (k < D ? -2 : 0)); }
@@ -190,10 +157,10 @@ __global__ void __launch_bounds__(256) k_bdqn_l1_cores(BdqnL1Compact p) {
             u4v xb[2];
 #pragma unroll
             for (int u = 0; u < 2; u++) {
-                xb[u][0] = pack_i((int8_t)cur[u][s][0], (int8_t)(cur[u][s][0] >> 8));
-                xb[u][1] = pack_i((int8_t)(cur[u][s][0] >> 16), (int8_t)(cur[u][s][0] >> 24));
-                xb[u][2] = pack_i((int8_t)cur[u][s][1], (int8_t)(cur[u][s][1] >> 8));
-                xb[u][3] = pack_i((int8_t)(cur[u][s][1] >> 16), (int8_t)(cur[u][s][1] >> 24));
+                xb[u][0] = pack_i8((int8_t)cur[u][s][0], (int8_t)(cur[u][s][0] >> 8));
+                xb[u][1] = pack_i8((int8_t)(cur[u][s][0] >> 16), (int8_t)(cur[u][s][0] >> 24));
+                xb[u][2] = pack_i8((int8_t)cur[u][s][1], (int8_t)(cur[u][s][1] >> 8));
+                xb[u][3] = pack_i8((int8_t)(cur[u][s][1] >> 16), (int8_t)(cur[u][s][1] >> 24));
             }
 #pragma unroll
             for (int t = 0; t < 3; t++)
@@ -421,10 +388,10 @@ __global__ void __launch_bounds__(64 * kActWaves) k_bdqn_act(BdqnAct p) {
             for (int c = 0; c < NC; c++) {
                 const uint32_t* xr = reinterpret_cast<const uint32_t*>(p.x + (size_t)rc[c] * p.x_stride);
                 const uint32_t x0 = d0 < x4 ? xr[d0] : 0u, x1 = d0 + 1 < x4 ? xr[d0 + 1] : 0u;
-                xb[c][0] = pack_i((int8_t)x0, (int8_t)(x0 >> 8));
-                xb[c][1] = pack_i((int8_t)(x0 >> 16), (int8_t)(x0 >> 24));
-                xb[c][2] = pack_i((int8_t)x1, (int8_t)(x1 >> 8));
-                xb[c][3] = pack_i((int8_t)(x1 >> 16), (int8_t)(x1 >> 24));
+                xb[c][0] = pack_i8((int8_t)x0, (int8_t)(x0 >> 8));
+                xb[c][1] = pack_i8((int8_t)(x0 >> 16), (int8_t)(x0 >> 24));
+                xb[c][2] = pack_i8((int8_t)x1, (int8_t)(x1 >> 8));
+                xb[c][3] = pack_i8((int8_t)(x1 >> 16), (int8_t)(x1 >> 24));
             }
 #pragma unroll
             for (int mt = 0; mt < 8; mt++) {
@@ -500,7 +467,7 @@ __global__ void __launch_bounds__(64 * kActWaves) k_bdqn_act(BdqnAct p) {
                 v[e] = h[2 * s][e];
                 v[4 + e] = h[2 * s + 1][e];
             }
-            split8(v, hb[s][0], hb[s][1], hb[s][2]);
+            split3(v, hb[s][0], hb[s][1], hb[s][2]);
         }
         f4 acc[8];
 #pragma unroll
@@ -533,7 +500,7 @@ __global__ void __launch_bounds__(64 * kActWaves) k_bdqn_act(BdqnAct p) {
                 v[e] = out[2 * s][e];
                 v[4 + e] = out[2 * s + 1][e];
             }
-            split8(v, bf[c][s][0], bf[c][s][1], bf[c][s][2]);
+            split3(v, bf[c][s][0], bf[c][s][1], bf[c][s][2]);
         }
     }
     bool explore[NC];

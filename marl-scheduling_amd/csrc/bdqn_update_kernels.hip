@@ -32,29 +32,22 @@
 #include <stdint.h>
 
 #include "ms_bdqn.h"
+#include "ms_mfma.h"
 
 namespace ms {
 
 namespace {
 
-typedef float f4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t u4v __attribute__((ext_vector_type(4)));
-
 constexpr int kUpdK = 128;  // layer-1 K chunk
 
-__device__ __forceinline__ f4 mfma4(float a, float b, f4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-__device__ __forceinline__ f4 mfma_bf16(const u4v& a, const u4v& b, f4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0,
-                                                   0);
-}
-__device__ __forceinline__ float trunc_bf16(float x) { return __uint_as_float(__float_as_uint(x) & 0xffff0000u); }
+// This unit keeps its own packing (a shift and an or) and the split and int8 pairs built on it: with ms_mfma.h's
+// pack_hi (one v_perm_b32) k_bdqn_upd_l1 and k_bdqn_upd_w1 compile to other code.
 // two values exact in bf16 -> one dword (element 2t = low half)
 __device__ __forceinline__ uint32_t pack2(float lo, float hi) {
     return (__float_as_uint(lo) >> 16) | (__float_as_uint(hi) & 0xffff0000u);
 }
 // eight f32 values as three exact bf16 terms (hi + mid + lo == v: each term keeps 8 significant bits)
-__device__ __forceinline__ void split8(const float (&v)[8], u4v& hi, u4v& mid, u4v& lo) {
+__device__ __forceinline__ void split3_pack2(const float (&v)[8], u4v& hi, u4v& mid, u4v& lo) {
 #pragma unroll
     for (int t = 0; t < 4; t++) {
         float h[2], m[2], l[2];
@@ -71,7 +64,7 @@ __device__ __forceinline__ void split8(const float (&v)[8], u4v& hi, u4v& mid, u
         lo[t] = pack2(l[0], l[1]);
     }
 }
-__device__ __forceinline__ uint32_t pack_i8(int a, int b) { return pack2((float)a, (float)b); }
+__device__ __forceinline__ uint32_t pack2_i8(int a, int b) { return pack2((float)a, (float)b); }
 __device__ __forceinline__ float clampg(float g, float c) { return g < -c ? -c : (g > c ? c : g); }  // NaN stays
 
 // head row o of a net: the Mn advantage rows, then the value row; NULL past it
@@ -166,12 +159,12 @@ __global__ void __launch_bounds__(256) k_bdqn_upd_l1(BdqnUpd p) {
             for (int t = 0; t < 4; t++) {
                 const uint32_t dw = xr[s][bt][t >> 1];
                 const int sh = 16 * (t & 1);
-                xb[bt][t] = pack_i8((int)(int8_t)(dw >> sh), (int)(int8_t)(dw >> (sh + 8)));
+                xb[bt][t] = pack2_i8((int)(int8_t)(dw >> sh), (int)(int8_t)(dw >> (sh + 8)));
             }
 #pragma unroll
         for (int ht = 0; ht < 4; ht++) {
             u4v a3[3];
-            split8(wr[s][ht], a3[0], a3[1], a3[2]);
+            split3_pack2(wr[s][ht], a3[0], a3[1], a3[2]);
 #pragma unroll
             for (int bt = 0; bt < 4; bt++)
 #pragma unroll
@@ -637,14 +630,14 @@ __global__ void __launch_bounds__(256) k_bdqn_upd_w1(BdqnUpd p) {
             float v[8];
 #pragma unroll
             for (int e = 0; e < 8; e++) v[e] = dp[(bb + e) * kW1DP + 32 * w + 16 * ht + i];
-            split8(v, a3[ht][0], a3[ht][1], a3[ht][2]);
+            split3_pack2(v, a3[ht][0], a3[ht][1], a3[ht][2]);
         }
 #pragma unroll
         for (int kt = 0; kt < 4; kt++) {
             u4v xb;
 #pragma unroll
             for (int t = 0; t < 4; t++)
-                xb[t] = pack_i8((int8_t)xb8[(bb + 2 * t) * 64 + 16 * kt + i], (int8_t)xb8[(bb + 2 * t + 1) * 64 + 16 * kt + i]);
+                xb[t] = pack2_i8((int8_t)xb8[(bb + 2 * t) * 64 + 16 * kt + i], (int8_t)xb8[(bb + 2 * t + 1) * 64 + 16 * kt + i]);
 #pragma unroll
             for (int ht = 0; ht < 2; ht++)
 #pragma unroll

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "ms_layout.h"
+#include "ms_env_launch.h"  // env_step_act_supported, env_rollout_free_supported
 #include "ms_dqn.h"
 #include "ms_bdqn.h"
 #include "ms_wide.h"
@@ -29,12 +30,10 @@ hipError_t launch_env_step(const Params&, int64_t, uint8_t*, uint32_t*, Liab*, c
                            hipStream_t);
 hipError_t launch_env_step_act(const Params&, int64_t, uint8_t*, uint32_t*, Liab*, const StepIO&, const FusedAct&,
                                uint64_t, hipStream_t);
-bool env_step_act_supported(const Params&, int64_t);
 hipError_t launch_env_rollout_act(const Params&, int64_t, uint8_t*, uint32_t*, Liab*, const StepIO&, const FusedAct&,
                                   const RoundStride&, int, int, uint64_t, hipStream_t);
 hipError_t launch_env_rollout_act_free(const Params&, int64_t, uint8_t*, uint32_t*, Liab*, const StepIO&,
                                        const FusedActFree&, const RoundStrideFree&, int, int, hipStream_t);
-bool env_rollout_free_supported(const Params&);
 void acc_common_tables(const void*, const uint32_t**, int*);
 hipError_t launch_env_fill_common(const Params&, int64_t, const StepIO&, const FusedActFree&, const RoundStrideFree&,
                                   int, int, hipStream_t);

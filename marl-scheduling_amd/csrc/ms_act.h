@@ -1,6 +1,6 @@
 // ms_act.h — the forward pass of the acting nets, shared by the sampling and greedy act kernels
 // (ms_act_kernels.h, policy_kernels.hip, act_pair_kernels.hip, greedy_kernels.hip) and the env round's
-// fused acting of fixed-price global nets (env_kernels.hip): Philox2x32 uniforms, the clamped row load,
+// fused acting of fixed-price global nets (ms_env_round.h): Philox2x32 uniforms, the clamped row load,
 // the exact three-term bf16 layer 1 (W1Split), the 16-wide head with its logits and its softmax /
 // Categorical sampling (Head) and the act fragment block layout (ms_act_prepare).
 // PPOmodules.py:53-63 (ActorCritic.act).
@@ -18,55 +18,11 @@
 
 #pragma clang fp contract(fast)
 
+#include "ms_mfma.h"  // f4 / u4v, mfma4, mfma_bf16, pack_hi, trunc_bf16, bytes_to_bf16, fast_tanh_b, fast_exp, fast_log (under the contraction set above)
+
 namespace ms {
 
-typedef float f4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ f4 mfma4(float a, float b, f4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-
 // (mulhilo, philox2 and u24 live in ms_common.h: the PPO gradient regenerates acting draws with them)
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t u4v __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ f4 mfma_bf16(const u4v& a, const u4v& b, f4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0,
-                                                   0);
-}
-
-// tanh(x) = 1 - 2 / (1 + exp(2x)): exp overflows to inf for large x (-> 1) and underflows to 0 for
-// large -x (-> -1); absolute error ~1e-7 (what feeds the next layers' sums of O(1) terms).
-// tanh(a + b) with the bias pre-scaled, bs = b * 2 log2(e) (kTanhScale): the exponent is one fma
-constexpr float kTanhScale = 2.8853900817779268f;
-__device__ __forceinline__ float fast_tanh_b(float a, float bs) {
-    const float t = __builtin_amdgcn_exp2f(fmaf(a, kTanhScale, bs));  // exp(2(a + b))
-    return fmaf(-2.f, __builtin_amdgcn_rcpf(1.f + t), 1.f);
-}
-__device__ __forceinline__ float fast_exp(float x) { return __builtin_amdgcn_exp2f(x * 1.4426950408889634f); }
-// exp(x - m) as exp2(x log2e - m log2e) with one fma (m_l2e = m * log2e)
-__device__ __forceinline__ float fast_exp_sub(float x, float m_l2e) {
-    return __builtin_amdgcn_exp2f(fmaf(x, 1.4426950408889634f, -m_l2e));
-}
-__device__ __forceinline__ float fast_log(float x) { return __builtin_amdgcn_logf(x) * 0.69314718055994531f; }
-
-// bf16 (upper half of the f32 bits) of elements 2i, 2i+1 packed into one dword
-__device__ __forceinline__ uint32_t pack_hi(float lo, float hi) {
-    return __builtin_amdgcn_perm(__float_as_uint(hi), __float_as_uint(lo), 0x07060302u);  // one v_perm_b32
-}
-__device__ __forceinline__ float trunc_bf16(float x) { return __uint_as_float(__float_as_uint(x) & 0xffff0000u); }
-
-// int8 observation bytes (two dwords = 8 consecutive inputs) as a bf16 B fragment (exact)
-__device__ __forceinline__ u4v bytes_to_bf16(uint32_t d0, uint32_t d1) {
-    u4v r;
-#pragma unroll
-    for (int d = 0; d < 4; d++) {
-        const uint32_t src = d < 2 ? d0 : d1;
-        const int sh = 16 * (d & 1);
-        const float a = (float)(int8_t)(src >> sh);
-        const float b = (float)(int8_t)(src >> (sh + 8));
-        r[d] = pack_hi(a, b);
-    }
-    return r;
-}
 
 // A tile's rows as loaded: lane (j, g4) takes dwords 8s + 2 g4, 8s + 2 g4 + 1 of its row j, exactly its B
 // fragment of k-step s. Unconditional loads from clamped addresses, used as loaded: the dwords past the

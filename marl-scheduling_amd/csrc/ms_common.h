@@ -152,6 +152,21 @@ struct RawBuf {
     }
 };
 
+// p advanced by a byte stride (a NULL array stays NULL): round t's slice of a per-round array
+template <class T>
+__device__ __forceinline__ T* advance(T* p, int64_t bytes) {
+    return p ? reinterpret_cast<T*>(reinterpret_cast<uintptr_t>(p) + bytes) : p;
+}
+
+// x / d for 0 <= x < 256 and 1 <= d < 256 without the integer-division sequence: floor((x + 1/2) * rcp(d)).
+// (x + 1/2) / d lies at least 1/(2d) >= 2^-9 from an integer and the product's error is below
+// 256 * 2^-21 = 2^-13 (rcp within 2 ulp), so the floor is exact; checked exhaustively over the range
+// with the reciprocal perturbed by +-2 ulp (tests/test_env_helpers.py). An add feeding a multiply: no fma can
+// form from it, so every includer gets this code whatever its contraction mode.
+__device__ __forceinline__ int small_div(int x, int d) {
+    return (int)(((float)x + 0.5f) * __builtin_amdgcn_rcpf((float)d));
+}
+
 typedef uint32_t u4a __attribute__((ext_vector_type(4), aligned(4)));  // 4-byte aligned 16-byte load
 
 template <int LPR>

@@ -173,7 +173,7 @@ struct MixIO {
     int8_t* off_taken;   // [E][N][L] or NULL
 };
 
-// the fused next-round acting of ms_env_step_act (env_kernels.hip fused_act)
+// the fused next-round acting of ms_env_step_act (ms_env_round.h fused_act)
 struct FusedAct {
     ms_mlp_params off, acc;
     const int8_t* common;

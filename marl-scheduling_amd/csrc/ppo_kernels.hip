@@ -30,13 +30,10 @@
 
 #include "../../include/marlsched.h"
 #include "ms_common.h"
+#include "ms_mfma.h"
 #include "ms_ppo.h"
 
 namespace ms {
-
-typedef float f4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ f4 mfma4(float a, float b, f4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
 
 __device__ __forceinline__ float xsum16(float v) {  // sum over the 16 lanes sharing lane>>4
     v += __shfl_xor(v, 1);
@@ -48,55 +45,8 @@ __device__ __forceinline__ float xsum16(float v) {  // sum over the 16 lanes sha
 __device__ __forceinline__ float xsum4g(float v) { return rows_sum(v); }  // sum over lanes j, j+16, j+32, j+48
 __device__ __forceinline__ float xmax4g(float v) { return rows_max(v); }
 
-// tanh(x) = 1 - 2 / (1 + exp(2x)): exp overflows to inf for large x (-> 1) and underflows to 0 for
-// large -x (-> -1); absolute error ~1e-7 (what feeds the next layers' sums of O(1) terms).
-// tanh(a + b) with the bias pre-scaled, bs = b * 2 log2(e) (kTanhScale): the exponent is one fma
-constexpr float kTanhScale = 2.8853900817779268f;
-__device__ __forceinline__ float fast_tanh_b(float a, float bs) {
-    const float t = __builtin_amdgcn_exp2f(fmaf(a, kTanhScale, bs));  // exp(2(a + b))
-    return fmaf(-2.f, __builtin_amdgcn_rcpf(1.f + t), 1.f);
-}
-__device__ __forceinline__ float fast_exp(float x) { return __builtin_amdgcn_exp2f(x * 1.4426950408889634f); }
-// exp(x - m) as exp2(x log2e - m log2e) with one fma (m_l2e = m * log2e)
-__device__ __forceinline__ float fast_exp_sub(float x, float m_l2e) {
-    return __builtin_amdgcn_exp2f(fmaf(x, 1.4426950408889634f, -m_l2e));
-}
-__device__ __forceinline__ float fast_log(float x) { return __builtin_amdgcn_logf(x) * 0.69314718055994531f; }
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t u4v __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ f4 mfma_bf16(const u4v& a, const u4v& b, f4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0,
-                                                   0);
-}
-// bf16 (upper half of the f32 bits) of two floats packed into one dword
-__device__ __forceinline__ uint32_t pack_hi(float lo, float hi) {
-    return __builtin_amdgcn_perm(__float_as_uint(hi), __float_as_uint(lo), 0x07060302u);  // one v_perm_b32
-}
-__device__ __forceinline__ float trunc_bf16(float x) { return __uint_as_float(__float_as_uint(x) & 0xffff0000u); }
-
-// 8 floats as three bf16 fragments with v = hi + mid + lo exactly (truncation leaves exact residuals)
-__device__ __forceinline__ void split3(const float (&v)[8], u4v& hi, u4v& mid, u4v& lo) {
-#pragma unroll
-    for (int d = 0; d < 4; d++) {
-        float h[2], m[2], l[2];
-#pragma unroll
-        for (int t = 0; t < 2; t++) {
-            h[t] = trunc_bf16(v[2 * d + t]);
-            const float r = v[2 * d + t] - h[t];
-            m[t] = trunc_bf16(r);
-            l[t] = r - m[t];
-        }
-        hi[d] = pack_hi(h[0], h[1]);
-        mid[d] = pack_hi(m[0], m[1]);
-        lo[d] = pack_hi(l[0], l[1]);
-    }
-}
-
-// int8 values (exact in bf16) packed in pairs
-__device__ __forceinline__ uint32_t pack_i8(int a, int b) { return pack_hi((float)a, (float)b); }
-__device__ __forceinline__ u4v bytes_to_bf16(uint32_t d0, uint32_t d1) {
+// ms_mfma.h's bytes_to_bf16 written out pair by pair (the same values): k_ppo_grad compiles to other code with the loop form
+__device__ __forceinline__ u4v bytes_to_bf16_pairs(uint32_t d0, uint32_t d1) {
     u4v r;
     r[0] = pack_i8((int8_t)d0, (int8_t)(d0 >> 8));
     r[1] = pack_i8((int8_t)(d0 >> 16), (int8_t)(d0 >> 24));
@@ -324,7 +274,7 @@ __global__ void __launch_bounds__((64 * GradLds<NQ, NT, MODEX>::WPB), ((NQ * NT 
         f4 a1 = {0, 0, 0, 0}, c1 = {0, 0, 0, 0};
 #pragma unroll
         for (int s = 0; s < S1; s++) {
-            const u4v xb = bytes_to_bf16(xw[s][0], xw[s][1]);
+            const u4v xb = bytes_to_bf16_pairs(xw[s][0], xw[s][1]);
 #pragma unroll
             for (int t = 0; t < 3; t++) {
                 const u4v wa = *reinterpret_cast<const u4v*>(sW1s + (0 * 3 + t) * 16 * W1B + j * W1B + 32 * s + 8 * g4);

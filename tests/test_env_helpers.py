@@ -1,6 +1,6 @@
 """Host-side checks of arithmetic identities the env kernel relies on (no GPU).
 
-small_div (marl-scheduling_amd/csrc/env_kernels.hip): x / d for 0 <= x < 256, 1 <= d < 256 as
+small_div (marl-scheduling_amd/csrc/ms_common.h): x / d for 0 <= x < 256, 1 <= d < 256 as
 floor((x + 1/2) * rcp(d)) in float32. The device reciprocal (v_rcp_f32) is not correctly rounded,
 so the identity is checked with the reciprocal perturbed by up to +-2 ulp."""
 import numpy as np

@@ -4,7 +4,7 @@ them out of the update (no draws, frozen groups through ms_adam_step_dev_masked)
 Everything is compared bit for bit: the one-launch rollout against the launch pairs, the played trajectory against
 the object-faithful restatement (oracle/pyref.py), graph against eager, a resumed run against the uninterrupted one.
 
-Which kernel a case reaches (env_kernels.hip lanes_per_env): below 1024 replicas every shape here steps with 16
+Which kernel a case reaches (ms_env_launch.h lanes_per_env): below 1024 replicas every shape here steps with 16
 lanes per replica, i.e. the <16, DynShape> kernels, 4x4x3 included; the FixShape<4, 4, 3, 1> kernels run 4x4x3 from
 2049 to 4096 replicas (32 lanes), the <64, DynShape> ones from 1024 to 2048, the <32, DynShape> ones another shape
 from 2049 replicas. 6x5x2 at 40 replicas is outside the fused kernels' range (4 replicas a wave, 120 acceptor

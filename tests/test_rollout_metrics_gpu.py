@@ -4,7 +4,7 @@ paths instead of falling back to an act launch and an env launch per round.
 
 The accumulators must equal those of ms_env_step bit for bit, the two doubles included: quality_sum receives one
 inexact term per round (a price over a remaining time of 3 or 6), so inside one launch the order of its adds is
-part of the contract (env_kernels.hip: the group leader's ordered read-modify-write). Every test compares raw
+part of the contract (ms_env_round.h: the group leader's ordered read-modify-write). Every test compares raw
 bytes, with episode boundaries inside the launch (episode_length 7 against 20 or 21 rounds per rollout, 3 + 1
 slots that wrap across the two iterations), and asserts that the accumulators it compared are not empty."""
 import ctypes as ct

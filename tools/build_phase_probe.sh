@@ -1,6 +1,6 @@
 #!/usr/bin/env bash
 # Profiling-only build: libmarlsched with per-phase cycle counters in k_env_step (MS_PHASE_TIMING, see
-# env_kernels.hip), all sources as build.sh compiles them. Output: tools/_probe[_lpeN]/libmarlsched_probe.so.
+# ms_env_round.h; the read-outs are env_kernels.hip's), all sources as build.sh compiles them. Output: tools/_probe[_lpeN]/libmarlsched_probe.so.
 # The product library (marl-scheduling_amd/libmarlsched.so) is never built this way.
 set -euo pipefail
 HERE="$(cd "$(dirname "${BASH_SOURCE[0]}")" && pwd)"
