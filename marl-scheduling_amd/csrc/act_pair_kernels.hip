@@ -33,25 +33,17 @@ __global__ void __launch_bounds__(256, (S1b >= 4 ? 2 : MS_ACT_PAIR_MINB)) k_act_
 // both halves of a free-price round's acting in one launch when their shapes have a paired kernel
 // (cfg3: offer rows of <= 32 bytes, <= 16 actions; acceptor rows of <= 64 bytes, <= 32 actions),
 // else the two launches in order
-hipError_t launch_act_round(const ms_mlp_params* core, const ms_mlp_params* price, const int8_t* off_obs,
-                            int off_stride, int off_U, int off_S, const ms_mlp_params* acc,
-                            const int8_t* core_rows, const int8_t* core_owner, int acc_stride, int acc_U, int acc_S,
-                            int n_cores, const int8_t* common, int64_t E, uint64_t seed, uint64_t off_offset,
-                            uint64_t acc_offset, const uint64_t* offset_dev, int8_t* core_action, float* core_logprob,
-                            int8_t* price_state, int8_t* price_action, float* price_logprob, int8_t* env_price,
-                            int8_t* acc_action, float* acc_logprob, const float* ptab, const int16_t* pdigit,
-                            int pkeys, int64_t pus, hipStream_t st) {
-    if (!common || acc_stride < 16 || n_cores < 1 || acc_U % n_cores != 0) return hipErrorInvalidValue;
-    ActArgs c = compact_args(acc, core_rows, core_owner, acc_stride, E, acc_U, acc_S, n_cores, common, seed,
-                             acc_offset, offset_dev, nullptr, acc_action, acc_logprob);
-    const int s1a = s1_bucket(off_stride), nta = nt_bucket(core->n_actions);
-    const int s1b = s1_bucket(acc_stride), ntb = nt_bucket(acc->n_actions);
+hipError_t launch_act_round(ActArgs& o, ActArgs& c, hipStream_t st) {
+    if (!c.common || !c.owner || c.stride < 16 || c.n_cores < 1 || c.U % c.n_cores != 0) return hipErrorInvalidValue;
+    // one replica count; k_act_pair draws its own uniforms (EXT_U false)
+    if (o.E < 1 || c.E != o.E || o.uniforms || c.uniforms) return hipErrorInvalidValue;
+    const bool price = o.n2.n_groups > 0;
+    const int s1a = s1_bucket(o.stride), nta = nt_bucket(o.n1.n_actions);
+    const int s1b = s1_bucket(c.stride), ntb = nt_bucket(c.n1.n_actions);
     const bool unpaired = env_int("MS_ACT_UNPAIRED", 0) != 0;
     if (!price) {
         // a fixed-price round (cfg2): the offer units' one net (ActorCritic.act, k_act's single-net body) and the
         // compact acceptors in one launch
-        ActArgs o = act_args(core, off_obs, off_stride, E, off_U, off_S, seed, off_offset, offset_dev, nullptr,
-                             core_action, core_logprob);
         if (s1a != 1 || nta != 1 || s1b != 1 || ntb != 1 || unpaired) {
             hipError_t e = dispatch_act(o, st);
             return e != hipSuccess ? e : dispatch_act(c, st);
@@ -64,14 +56,8 @@ hipError_t launch_act_round(const ms_mlp_params* core, const ms_mlp_params* pric
         hipLaunchKernelGGL((k_act_pair<1, 1, 0, 1, 1>), dim3(ob + cb), dim3(256), 0, st, o, c, (int)ob);
         return hipGetLastError();
     }
-    if (price->in_dim != 4) return hipErrorInvalidValue;
-    ActArgs o = offer_free_args(core, price, off_obs, off_stride, E, off_U, off_S, n_cores, seed, off_offset,
-                                offset_dev, nullptr, core_action, core_logprob, price_state, price_action,
-                                price_logprob, env_price, pus);
-    o.ptab = ptab;
-    o.pdigit = pdigit;
-    o.pkeys = pkeys;
-    const bool price16 = nt_bucket(price->n_actions) == 1 && !unpaired;
+    if (o.n2.in_dim != 4) return hipErrorInvalidValue;
+    const bool price16 = nt_bucket(o.n2.n_actions) == 1 && !unpaired;
     const bool paired = s1a == 1 && nta == 1 && s1b == 2 && (ntb == 1 || ntb == 2) && price16;
     // cfg4's shapes (16 x 16 divided): 34-byte offer rows, 17 core actions, 99-byte acceptor rows, 49 actions
     const bool paired4 = s1a == 2 && (nta == 1 || nta == 2) && s1b == 4 && ntb != 0 && ntb <= 4 && price16;

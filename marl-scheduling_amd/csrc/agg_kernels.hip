@@ -20,6 +20,7 @@
 
 #include "../../include/marlsched.h"
 #include "ms_layout.h"
+#include "ms_returns.h"
 
 namespace ms {
 
@@ -122,11 +123,10 @@ __global__ void __launch_bounds__(256) k_decode_aggregated(const int32_t* __rest
     }
 }
 
-hipError_t launch_decode_aggregated(const int32_t* actions, long long EN, int C, int L, int O, int fully, int8_t* acc,
-                                    int8_t* off, int* bad, hipStream_t st) {
-    if (EN <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_decode_aggregated, dim3((unsigned)((EN + 255) / 256)), dim3(256), 0, st, actions, EN, C, L, O,
-                       fully, acc, off, bad);
+hipError_t launch_decode_aggregated(const DecodeArgs& a, hipStream_t st) {
+    if (a.EN <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_decode_aggregated, dim3((unsigned)((a.EN + 255) / 256)), dim3(256), 0, st, a.actions, a.EN,
+                       a.C, a.L, a.O, a.fully, a.acc, a.off, a.bad);
     return hipGetLastError();
 }
 

@@ -14,73 +14,14 @@
 #include <vector>
 
 #include "ms_layout.h"
-#include "ms_env_launch.h"  // env_step_act_supported, env_rollout_free_supported
+#include "ms_env_launch.h"
+#include "ms_act_args.h"
+#include "ms_returns.h"
 #include "ms_dqn.h"
 #include "ms_bdqn.h"
 #include "ms_wide.h"
 #include "ms_ppo.h"
 #include "ms_snapshot.h"
-
-namespace ms {
-hipError_t launch_bdqn_update(const BdqnUpd&, hipStream_t);
-hipError_t launch_env_init(const Params&, int64_t, uint8_t*, uint32_t*, Liab*, uint64_t, hipStream_t);
-hipError_t launch_env_reset(const Params&, int64_t, const uint8_t*, int8_t*, int8_t*, int8_t*, int8_t*, int8_t*,
-                            hipStream_t);
-hipError_t launch_env_step(const Params&, int64_t, uint8_t*, uint32_t*, Liab*, const StepIO&, const MixIO&,
-                           hipStream_t);
-hipError_t launch_env_step_act(const Params&, int64_t, uint8_t*, uint32_t*, Liab*, const StepIO&, const FusedAct&,
-                               uint64_t, hipStream_t);
-hipError_t launch_env_rollout_act(const Params&, int64_t, uint8_t*, uint32_t*, Liab*, const StepIO&, const FusedAct&,
-                                  const RoundStride&, int, int, uint64_t, hipStream_t);
-hipError_t launch_env_rollout_act_free(const Params&, int64_t, uint8_t*, uint32_t*, Liab*, const StepIO&,
-                                       const FusedActFree&, const RoundStrideFree&, int, int, hipStream_t);
-void acc_common_tables(const void*, const uint32_t**, int*);
-hipError_t launch_env_fill_common(const Params&, int64_t, const StepIO&, const FusedActFree&, const RoundStrideFree&,
-                                  int, int, hipStream_t);
-hipError_t launch_env_randbelow(const Params&, uint8_t*, uint32_t*, int64_t, uint32_t, uint32_t*, hipStream_t);
-hipError_t launch_env_auctioneer(const Params&, int64_t, uint8_t*, uint32_t*, int8_t*, hipStream_t);
-hipError_t launch_policy_act(const ms_mlp_params*, const int8_t*, int, int64_t, int, int, const int8_t*, uint64_t,
-                             uint64_t, const uint64_t*, const float*, int8_t*, float*, hipStream_t);
-hipError_t launch_policy_act_compact(const ms_mlp_params*, const int8_t*, const int8_t*, int, int64_t, int, int, int,
-                                     const int8_t*, uint64_t, uint64_t, const uint64_t*, const float*, int8_t*, float*,
-                                     hipStream_t);
-hipError_t launch_act_round(const ms_mlp_params*, const ms_mlp_params*, const int8_t*, int, int, int,
-                            const ms_mlp_params*, const int8_t*, const int8_t*, int, int, int, int, const int8_t*,
-                            int64_t, uint64_t, uint64_t, uint64_t, const uint64_t*, int8_t*, float*, int8_t*, int8_t*,
-                            float*, int8_t*, int8_t*, float*, const float*, const int16_t*, int, int64_t, hipStream_t);
-hipError_t launch_policy_act_greedy(const ms_mlp_params*, const int8_t*, int, int64_t, int, int, const int8_t*, int8_t*,
-                                    float*, hipStream_t);
-hipError_t launch_act_round_greedy(const ms_mlp_params*, const ms_mlp_params*, const int8_t*, int, int, int,
-                                   const ms_mlp_params*, const int8_t*, const int8_t*, int, int, int, int,
-                                   const int8_t*, int64_t, int8_t*, int8_t*, int8_t*, int8_t*, int8_t*, hipStream_t);
-hipError_t launch_price_table(const ms_mlp_params*, const int8_t*, int, float*, hipStream_t);
-size_t act_frag_bytes(const ms_mlp_params*, int);
-hipError_t launch_act_prepare(const ms_mlp_params*, const int8_t*, int, void*, hipStream_t);
-hipError_t launch_offer_act_free(const ms_mlp_params*, const ms_mlp_params*, const int8_t*, int, int64_t, int, int, int,
-                                 uint64_t, uint64_t, const uint64_t*, const float*, int8_t*, float*, int8_t*, int8_t*,
-                                 float*, int8_t*, int64_t, hipStream_t);
-hipError_t launch_returns(const float*, int, int64_t, int64_t, double, float*, hipStream_t);
-hipError_t launch_unit_returns(const void*, int, int, int64_t, int, const int32_t*, int, double, float*, hipStream_t);
-hipError_t launch_ppo_grad(const PpoArgs&, const GradOut&, hipStream_t);
-int ppo_param_count(int D, int A);
-int ppo_partial_rows(int n_chunks, bool keyed);
-hipError_t launch_aggregate_obs(const AggArgs&, hipStream_t);
-hipError_t launch_decode_aggregated(const int32_t*, long long, int, int, int, int, int8_t*, int8_t*, int*, hipStream_t);
-hipError_t launch_adam(const AdamTensor*, int, const double*, int, int64_t, double, double, double, const int64_t*,
-                       hipStream_t, const uint8_t* frozen = nullptr, int n_groups = 0);
-hipError_t launch_dqn_act(const DqnActArgs&, hipStream_t);
-hipError_t launch_regen_agent_rows(const RegenArgs&, hipStream_t);
-hipError_t launch_dqn_grad(const DqnGradArgs&, const DqnReduceArgs&, hipStream_t);
-hipError_t launch_bdqn_w1split(const float*, int, int, int, uint16_t*, hipStream_t);
-hipError_t launch_bdqn_l1_base(const float*, const float*, int, int, float*, float*, hipStream_t);
-hipError_t launch_bdqn_l1_compact(const BdqnL1Compact&, hipStream_t);
-hipError_t launch_bdqn_act(const BdqnAct&, hipStream_t);
-hipError_t launch_wide_act(const WideAct&, hipStream_t);
-hipError_t launch_wide_grad(const WideRows&, const WideGrads&, const WideReduce&, hipStream_t);
-hipError_t launch_snap_pack(const Params&, const SnapArgs&, const SnapHeader&, const uint8_t*, uint64_t*, hipStream_t);
-hipError_t launch_snap_unpack(const Params&, const SnapArgs&, hipStream_t);
-hipError_t launch_snap_validate(const Params&, const SnapArgs&, unsigned long long*, hipStream_t);
-}  // namespace ms
 
 // work split of k_ppo_grad: ~kGradWaves wave chunks over all groups (4 per block), >= 8 tiles of 16 rows each
 #ifndef MS_GRAD_WAVES
@@ -97,14 +38,9 @@ static void ppo_split(int64_t rows, int G, int* chunk_tiles, int* n_chunks) {
     *n_chunks = (int)((nc + 3) / 4 * 4);
 }
 
-struct ms_env {
+struct ms_env : ms::EnvDev {  // (P, E, recs, mt, liab: what the env launchers take)
     ms_config cfg;
-    ms::Params P;
-    int64_t E;
     int device;
-    uint8_t* recs;
-    uint32_t* mt;
-    ms::Liab* liab;
     uint32_t* scratch_u32;  // device word for randbelow
     uint32_t* err_host;     // sticky error word in host-coherent memory: set by a round that raised a
                             // fatal per-env flag (ms_layout.h kFatalFlags), read by ms_env_step without a sync
@@ -162,6 +98,18 @@ static int validate_config(const ms_config* c) {
 }
 
 static int cap_of(const ms_config* c) { return c->liability_cap > 0 ? c->liability_cap : 128; }
+
+// the fields every acting launch sets (A: ms::ActArgs or ms::GreedyArgs): the net, its rows, and the units' split
+// into S per group; everything else zero (a single net, Philox draws, no common row). The kernels count rows in
+// ints: more than that many become no replicas at all, which every dispatcher refuses.
+template <class A>
+static A act_shape(const ms_mlp_params* p, const int8_t* obs, int32_t stride, int64_t E, int32_t U, int32_t S) {
+    A a{};
+    a.n1 = *p, a.obs = obs, a.stride = stride;
+    a.U = U, a.S = S;
+    a.E = E * (int64_t)U <= 0x7fffffffll ? (int)E : 0, a.n_items = a.E * S;
+    return a;
+}
 
 extern "C" {
 
@@ -232,7 +180,7 @@ int ms_env_create(const ms_config* cfg, int64_t n_envs, uint64_t seed, ms_env** 
         return fail(MS_ENOMEM, "device allocation of %zu bytes failed", rec_b + mt_b + liab_b);
     }
     *env->err_host = 0;
-    hipError_t e = ms::launch_env_init(env->P, n_envs, env->recs, env->mt, env->liab, seed, nullptr);
+    hipError_t e = ms::launch_env_init(*env, seed, nullptr);
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e != hipSuccess) {
         ms_env_destroy(env);
@@ -254,18 +202,19 @@ int64_t ms_env_round(const ms_env* env) {
 
 int ms_env_reset(ms_env* env, const ms_obs_out* obs, void* stream) {
     if (!env || !obs) return fail(MS_EINVAL, "env/obs is NULL");
-    HIP_TRY(ms::launch_env_reset(env->P, env->E, env->recs, obs->acceptor, obs->offer, obs->auctioneer, obs->core_rows,
-                                 obs->core_owner,
-                                 (hipStream_t)stream));
+    ms::StepIO io{};
+    io.obs_acc = obs->acceptor, io.obs_off = obs->offer, io.obs_auct = obs->auctioneer;
+    io.obs_crow = obs->core_rows, io.obs_cown = obs->core_owner;
+    HIP_TRY(ms::launch_env_reset(*env, io, (hipStream_t)stream));
     return MS_OK;
 }
 
-struct RolloutArgs {
+struct FixedRollout {  // the rounds of one ms_env_rollout_act call
     ms::RoundStride st;
     int n_rounds, act_last;
 };
 static int env_step_impl(ms_env* env, const ms_actions* act, const ms_obs_out* obs, const ms_reward_out* rew,
-                         const ms_event_out* ev, const ms::FusedAct* fa, const RolloutArgs* ro, void* stream,
+                         const ms_event_out* ev, const ms::FusedAct* fa, const FixedRollout* ro, void* stream,
                          const ms::MixIO* mix = nullptr);
 static int fused_mixed_check(const ms_env* env, const ms_actions* act, uint64_t hc_mask, const char* who);
 static int fill_io(ms_env* env, const ms_actions* act, const ms_obs_out* obs, const ms_reward_out* rew,
@@ -337,7 +286,7 @@ static int rollout_act_impl(ms_env* env, const ms_actions* act, const ms_obs_out
     if (rew && (rew->price || rew->aggregated_offer || rew->aggregated_acceptor))
         return fail(MS_EINVAL, "ms_env_rollout_act: no price / aggregated reward outputs");
     const ms_round_strides& r = *strides;
-    RolloutArgs ro{{r.acceptor_action, r.offer_action, r.core_rows, r.core_owner, r.offer_obs, r.offer_reward,
+    FixedRollout ro{{r.acceptor_action, r.offer_action, r.core_rows, r.core_owner, r.offer_obs, r.offer_reward,
                     r.acceptor_reward, r.agent_reward, r.auctioneer_reward, r.next_off_action, r.next_off_logprob,
                     r.next_acc_action, r.next_acc_logprob, r.offset_step},
                    n_rounds, act_after_last ? 1 : 0};
@@ -390,7 +339,7 @@ int ms_env_step_act_supported(const ms_env* env) {
 }
 
 static int env_step_impl(ms_env* env, const ms_actions* act, const ms_obs_out* obs, const ms_reward_out* rew,
-                         const ms_event_out* ev, const ms::FusedAct* fa, const RolloutArgs* ro, void* stream,
+                         const ms_event_out* ev, const ms::FusedAct* fa, const FixedRollout* ro, void* stream,
                          const ms::MixIO* mix) {
     if (!env || !act) return fail(MS_EINVAL, "env/actions is NULL");
     if (!act->acceptor != !act->offer_core)
@@ -407,14 +356,12 @@ static int env_step_impl(ms_env* env, const ms_actions* act, const ms_obs_out* o
     if (rc != MS_OK) return rc;
     // (the fused launches take the mask alone: their rounds write the rules' picks into the action arrays)
     if (ro)
-        HIP_TRY(ms::launch_env_rollout_act(env->P, env->E, env->recs, env->mt, env->liab, io, *fa, ro->st, ro->n_rounds,
-                                           ro->act_last, mix ? mix->hc_mask : 0, (hipStream_t)stream));
+        HIP_TRY(ms::launch_env_rollout_act(*env, io, *fa, ro->st, ro->n_rounds, ro->act_last, mix ? mix->hc_mask : 0,
+                                           (hipStream_t)stream));
     else if (fa)
-        HIP_TRY(ms::launch_env_step_act(env->P, env->E, env->recs, env->mt, env->liab, io, *fa,
-                                        mix ? mix->hc_mask : 0, (hipStream_t)stream));
+        HIP_TRY(ms::launch_env_step_act(*env, io, *fa, mix ? mix->hc_mask : 0, (hipStream_t)stream));
     else
-        HIP_TRY(ms::launch_env_step(env->P, env->E, env->recs, env->mt, env->liab, io, mix ? *mix : ms::MixIO{},
-                                    (hipStream_t)stream));
+        HIP_TRY(ms::launch_env_step(*env, io, mix ? *mix : ms::MixIO{}, (hipStream_t)stream));
     env->round += ro ? ro->n_rounds : 1;
     return MS_OK;
 }
@@ -521,8 +468,7 @@ int ms_env_rollout_act_free(ms_env* env, const ms_actions* act, const ms_obs_out
     if (rc != MS_OK) return rc;
     const ms::FusedActFree fa = free_act_args(*next);
     const ms::RoundStrideFree st = free_strides(*strides);
-    HIP_TRY(ms::launch_env_rollout_act_free(P, env->E, env->recs, env->mt, env->liab, io, fa, st, n_rounds,
-                                            act_after_last ? 1 : 0, (hipStream_t)stream));
+    HIP_TRY(ms::launch_env_rollout_act_free(*env, io, fa, st, n_rounds, act_after_last ? 1 : 0, (hipStream_t)stream));
     if (!next->defer_common)
         HIP_TRY(ms::launch_env_fill_common(P, env->E, io, fa, st, n_rounds, act_after_last ? 1 : 0, (hipStream_t)stream));
     env->round += n_rounds;
@@ -567,7 +513,7 @@ int ms_env_randbelow(ms_env* env, int64_t e, uint32_t n, uint32_t* out, void* st
     if (!env || !out) return fail(MS_EINVAL, "env/out is NULL");
     if (e < 0 || e >= env->E) return fail(MS_EINVAL, "env index out of range");
     if (n < 1) return fail(MS_EINVAL, "n must be >= 1");
-    HIP_TRY(ms::launch_env_randbelow(env->P, env->recs, env->mt, e, n, env->scratch_u32, (hipStream_t)stream));
+    HIP_TRY(ms::launch_env_randbelow(*env, e, n, env->scratch_u32, (hipStream_t)stream));
     HIP_TRY(hipMemcpyAsync(out, env->scratch_u32, 4, hipMemcpyDeviceToHost, (hipStream_t)stream));
     HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
     return MS_OK;
@@ -575,7 +521,7 @@ int ms_env_randbelow(ms_env* env, int64_t e, uint32_t n, uint32_t* out, void* st
 
 int ms_env_auctioneer(ms_env* env, int8_t* actions, void* stream) {
     if (!env || !actions) return fail(MS_EINVAL, "env/actions is NULL");
-    HIP_TRY(ms::launch_env_auctioneer(env->P, env->E, env->recs, env->mt, actions, (hipStream_t)stream));
+    HIP_TRY(ms::launch_env_auctioneer(*env, actions, (hipStream_t)stream));
     return MS_OK;
 }
 
@@ -859,8 +805,10 @@ int ms_policy_act(const ms_mlp_params* p, const int8_t* obs, int32_t obs_stride,
     int rc = check_mlp(p, obs_stride, n_units, units_per_group);
     if (rc) return rc;
     if (n_envs < 1) return fail(MS_EINVAL, "n_envs must be >= 1");
-    HIP_TRY(ms::launch_policy_act(p, obs, obs_stride, n_envs, n_units, units_per_group, nullptr, seed, offset,
-                                  offset_dev, uniforms, action, logprob, (hipStream_t)stream));
+    ms::ActArgs a = act_shape<ms::ActArgs>(p, obs, obs_stride, n_envs, n_units, units_per_group);
+    a.seed = seed, a.offset = offset, a.offset_dev = offset_dev, a.uniforms = uniforms;
+    a.action = action, a.logprob = logprob;
+    HIP_TRY(ms::dispatch_act(a, (hipStream_t)stream));
     return MS_OK;
 }
 
@@ -872,8 +820,11 @@ int ms_policy_act_common(const ms_mlp_params* p, const int8_t* obs, int32_t obs_
     int rc = check_mlp(p, obs_stride, n_units, units_per_group);
     if (rc) return rc;
     if (n_envs < 1) return fail(MS_EINVAL, "n_envs must be >= 1");
-    HIP_TRY(ms::launch_policy_act(p, obs, obs_stride, n_envs, n_units, units_per_group, common_row, seed, offset,
-                                  offset_dev, uniforms, action, logprob, (hipStream_t)stream));
+    ms::ActArgs a = act_shape<ms::ActArgs>(p, obs, obs_stride, n_envs, n_units, units_per_group);
+    a.common = common_row;
+    a.seed = seed, a.offset = offset, a.offset_dev = offset_dev, a.uniforms = uniforms;
+    a.action = action, a.logprob = logprob;
+    HIP_TRY(ms::dispatch_act(a, (hipStream_t)stream));
     return MS_OK;
 }
 
@@ -887,9 +838,11 @@ int ms_policy_act_compact(const ms_mlp_params* p, const int8_t* core_rows, const
     if (n_envs < 1) return fail(MS_EINVAL, "n_envs must be >= 1");
     if (n_cores < 1 || n_units % n_cores != 0) return fail(MS_EINVAL, "n_units must be n_agents * n_cores");
     if (obs_stride < 16) return fail(MS_EINVAL, "obs_stride must be >= 16");
-    HIP_TRY(ms::launch_policy_act_compact(p, core_rows, core_owner, obs_stride, n_envs, n_units, units_per_group,
-                                          n_cores, common_row, seed, offset, offset_dev, uniforms, action, logprob,
-                                          (hipStream_t)stream));
+    ms::ActArgs a = act_shape<ms::ActArgs>(p, core_rows, obs_stride, n_envs, n_units, units_per_group);
+    a.owner = core_owner, a.n_cores = n_cores, a.common = common_row;
+    a.seed = seed, a.offset = offset, a.offset_dev = offset_dev, a.uniforms = uniforms;
+    a.action = action, a.logprob = logprob;
+    HIP_TRY(ms::dispatch_act(a, (hipStream_t)stream));
     return MS_OK;
 }
 
@@ -928,12 +881,20 @@ int ms_act_round_free(const ms_mlp_params* core, const ms_mlp_params* price, con
         return fail(MS_EINVAL, "price_table needs digit, table and n_keys >= 1");
     if (price_unit_stride != 0 && price_unit_stride < n_envs)
         return fail(MS_EINVAL, "price_unit_stride must be 0 or >= n_envs");
-    HIP_TRY(ms::launch_act_round(core, price, off_obs, off_stride, off_units, off_units_per_group, acc, core_rows,
-                                 core_owner, acc_stride, acc_units, acc_units_per_group, n_cores, common_row, n_envs,
-                                 seed, off_offset, acc_offset, offset_dev, core_action, core_logprob, price_state,
-                                 price_action, price_logprob, env_price, acc_action, acc_logprob,
-                                 price_table ? price_table->table : nullptr, price_table ? price_table->digit : nullptr,
-                                 price_table ? price_table->n_keys : 0, price_unit_stride, (hipStream_t)stream));
+    ms::ActArgs o = act_shape<ms::ActArgs>(core, off_obs, off_stride, n_envs, off_units, off_units_per_group);
+    o.seed = seed, o.offset = off_offset, o.offset_dev = offset_dev;
+    o.action = core_action, o.logprob = core_logprob;
+    if (price) {
+        o.n2 = *price, o.n_cores = n_cores;
+        o.price_state = price_state, o.price_action = price_action, o.price_logprob = price_logprob;
+        o.env_price = env_price, o.pus = price_unit_stride;
+        if (price_table) o.ptab = price_table->table, o.pdigit = price_table->digit, o.pkeys = price_table->n_keys;
+    }
+    ms::ActArgs c = act_shape<ms::ActArgs>(acc, core_rows, acc_stride, n_envs, acc_units, acc_units_per_group);
+    c.owner = core_owner, c.n_cores = n_cores, c.common = common_row;
+    c.seed = seed, c.offset = acc_offset, c.offset_dev = offset_dev;
+    c.action = acc_action, c.logprob = acc_logprob;
+    HIP_TRY(ms::launch_act_round(o, c, (hipStream_t)stream));
     return MS_OK;
 }
 
@@ -951,9 +912,9 @@ int ms_policy_act_greedy(const ms_mlp_params* p, const int8_t* obs, int32_t obs_
     int rc = check_mlp(p, obs_stride, n_units, units_per_group);
     if (rc) return rc;
     if (n_envs < 1) return fail(MS_EINVAL, "n_envs must be >= 1");
-    return greedy_rc(ms::launch_policy_act_greedy(p, obs, obs_stride, n_envs, n_units, units_per_group, common_row,
-                                                  action, logprob, (hipStream_t)stream),
-                     "ms_policy_act_greedy");
+    ms::GreedyArgs a = act_shape<ms::GreedyArgs>(p, obs, obs_stride, n_envs, n_units, units_per_group);
+    a.common = common_row, a.action = action, a.logprob = logprob;
+    return greedy_rc(ms::dispatch_greedy(a, (hipStream_t)stream), "ms_policy_act_greedy");
 }
 
 int ms_act_round_greedy(const ms_mlp_params* core, const ms_mlp_params* price, const int8_t* off_obs, int32_t off_stride,
@@ -983,11 +944,12 @@ int ms_act_round_greedy(const ms_mlp_params* core, const ms_mlp_params* price, c
         return fail(MS_EINVAL, "core chooser must be (2C+2) -> C+1");
     if (n_cores < 1 || acc_units % n_cores != 0)
         return fail(MS_EINVAL, "acceptor units must be n_agents * n_cores");
-    return greedy_rc(ms::launch_act_round_greedy(core, price, off_obs, off_stride, off_units, off_units_per_group, acc,
-                                                 core_rows, core_owner, acc_stride, acc_units, acc_units_per_group,
-                                                 n_cores, common_row, n_envs, core_action, price_state, price_action,
-                                                 env_price, acc_action, (hipStream_t)stream),
-                     "ms_act_round_greedy");
+    ms::GreedyArgs o = act_shape<ms::GreedyArgs>(core, off_obs, off_stride, n_envs, off_units, off_units_per_group);
+    o.n_cores = n_cores, o.action = core_action;
+    if (price) o.n2 = *price, o.price_state = price_state, o.price_action = price_action, o.env_price = env_price;
+    ms::GreedyArgs c = act_shape<ms::GreedyArgs>(acc, core_rows, acc_stride, n_envs, acc_units, acc_units_per_group);
+    c.owner = core_owner, c.n_cores = n_cores, c.common = common_row, c.action = acc_action;
+    return greedy_rc(ms::launch_act_round_greedy(o, c, (hipStream_t)stream), "ms_act_round_greedy");
 }
 
 int ms_price_table_build(const ms_mlp_params* price_chooser, const ms_price_table* t, void* stream) {
@@ -1033,9 +995,13 @@ int ms_offer_act_free(const ms_mlp_params* core, const ms_mlp_params* price, con
     if (n_envs < 1) return fail(MS_EINVAL, "n_envs must be >= 1");
     if (price_unit_stride != 0 && price_unit_stride < n_envs)
         return fail(MS_EINVAL, "price_unit_stride must be 0 or >= n_envs");
-    HIP_TRY(ms::launch_offer_act_free(core, price, obs, obs_stride, n_envs, n_units, units_per_group, n_cores, seed,
-                                      offset, offset_dev, uniforms, core_action, core_logprob, price_state,
-                                      price_action, price_logprob, env_price, price_unit_stride, (hipStream_t)stream));
+    ms::ActArgs a = act_shape<ms::ActArgs>(core, obs, obs_stride, n_envs, n_units, units_per_group);
+    a.n2 = *price, a.n_cores = n_cores;
+    a.seed = seed, a.offset = offset, a.offset_dev = offset_dev, a.uniforms = uniforms;
+    a.action = core_action, a.logprob = core_logprob;
+    a.price_state = price_state, a.price_action = price_action, a.price_logprob = price_logprob;
+    a.env_price = env_price, a.pus = price_unit_stride;
+    HIP_TRY(ms::dispatch_act(a, (hipStream_t)stream));
     return MS_OK;
 }
 
@@ -1227,17 +1193,10 @@ int ms_aggregate_obs(const ms_config* cfg, int64_t E, const int8_t* acc_obs, con
     if (E < 1 || !acc_obs || !off_obs) return fail(MS_EINVAL, "need E >= 1 and both divided observation arrays");
     const ms::Params P = ms::make_params(*cfg, cap_of(cfg));
     ms::AggArgs g{};
-    g.acc = acc_obs;
-    g.off = off_obs;
-    g.out_acc = agg_acceptor;
-    g.out_off = agg_offer;
-    g.out_full = fully;
-    g.N = P.N;
-    g.C = P.C;
-    g.L = P.L;
-    g.d_acc = P.d_acc;
-    g.acc_stride = P.acc_stride;
-    g.off_stride = P.off_stride;
+    g.acc = acc_obs, g.off = off_obs;
+    g.out_acc = agg_acceptor, g.out_off = agg_offer, g.out_full = fully;
+    g.N = P.N, g.C = P.C, g.L = P.L;
+    g.d_acc = P.d_acc, g.acc_stride = P.acc_stride, g.off_stride = P.off_stride;
     g.agg_acc_stride = ms::align4(P.C * P.d_acc);
     g.agg_off_stride = ms::align4(2 * P.C + 2 * P.L);
     g.full_stride = ms::align4(2 * P.C + 2 * P.L + P.C * P.d_acc);
@@ -1256,51 +1215,24 @@ int ms_decode_aggregated(const ms_config* cfg, int64_t E, const int32_t* actions
     for (int c = 0; c < P.C; c++) space *= (double)(P.O + 1);
     for (int s = 0; s < P.L; s++) space *= (double)(P.C + 1);
     if (space > 2147483647.0) return fail(MS_EINVAL, "aggregated action space (O+1)^C * (C+1)^L exceeds int32");
-    HIP_TRY(ms::launch_decode_aggregated(actions, (long long)E * P.N, P.C, P.L, P.O, fully ? 1 : 0, acceptor,
-                                         offer_core, n_bad, (hipStream_t)stream));
+    ms::DecodeArgs d{};
+    d.actions = actions, d.EN = (long long)E * P.N;
+    d.C = P.C, d.L = P.L, d.O = P.O, d.fully = fully ? 1 : 0;
+    d.acc = acceptor, d.off = offer_core, d.bad = n_bad;
+    HIP_TRY(ms::launch_decode_aggregated(d, (hipStream_t)stream));
     return MS_OK;
 }
 
 static_assert(sizeof(ms_adam_tensor) == sizeof(ms::AdamTensor), "ms_adam_tensor layout");
 static_assert(MS_ADAM_MAX_TENSORS == ms::kAdamMaxTensors, "ms_adam_tensor count");
 
-int ms_adam_step(const ms_adam_tensor* tensors, int32_t n_tensors, const double* lr, int32_t n_lr, int64_t step,
-                 double beta1, double beta2, double eps, void* stream) {
-    if (!tensors || !lr) return fail(MS_EINVAL, "NULL argument");
+// the three Adam entry points' shared checks and launch (step_dev NULL: the host's step; frozen NULL: no mask)
+static int adam_step(const ms_adam_tensor* tensors, int32_t n_tensors, const double* lr, int32_t n_lr, int64_t step,
+                     const int64_t* step_dev, double beta1, double beta2, double eps, int32_t n_groups,
+                     const uint8_t* frozen_dev, void* stream) {
     if (n_tensors < 1 || n_tensors > MS_ADAM_MAX_TENSORS) return fail(MS_EINVAL, "n_tensors must be in [1, %d]", MS_ADAM_MAX_TENSORS);
     if (n_lr < 1 || n_lr > ms::kAdamMaxGroups) return fail(MS_EINVAL, "n_lr must be in [1, %d]", ms::kAdamMaxGroups);
-    if (step < 1) return fail(MS_EINVAL, "step must be >= 1");
-    for (int i = 0; i < n_tensors; i++) {
-        const ms_adam_tensor& t = tensors[i];
-        if (!t.param || !t.grad || !t.exp_avg || !t.exp_avg_sq || t.numel < 0) return fail(MS_EINVAL, "bad tensor %d", i);
-        if (t.lr_group < 0 || t.lr_group >= n_lr) return fail(MS_EINVAL, "tensor %d: lr_group out of range", i);
-    }
-    HIP_TRY(ms::launch_adam(reinterpret_cast<const ms::AdamTensor*>(tensors), n_tensors, lr, n_lr, step, beta1, beta2,
-                            eps, nullptr, (hipStream_t)stream));
-    return MS_OK;
-}
-
-int ms_adam_step_dev(const ms_adam_tensor* tensors, int32_t n_tensors, const double* lr, int32_t n_lr,
-                     const int64_t* step_dev, double beta1, double beta2, double eps, void* stream) {
-    if (!tensors || !lr || !step_dev) return fail(MS_EINVAL, "NULL argument");
-    if (n_tensors < 1 || n_tensors > MS_ADAM_MAX_TENSORS) return fail(MS_EINVAL, "n_tensors must be in [1, %d]", MS_ADAM_MAX_TENSORS);
-    if (n_lr < 1 || n_lr > ms::kAdamMaxGroups) return fail(MS_EINVAL, "n_lr must be in [1, %d]", ms::kAdamMaxGroups);
-    for (int i = 0; i < n_tensors; i++) {
-        const ms_adam_tensor& t = tensors[i];
-        if (!t.param || !t.grad || !t.exp_avg || !t.exp_avg_sq || t.numel < 0) return fail(MS_EINVAL, "bad tensor %d", i);
-        if (t.lr_group < 0 || t.lr_group >= n_lr) return fail(MS_EINVAL, "tensor %d: lr_group out of range", i);
-    }
-    HIP_TRY(ms::launch_adam(reinterpret_cast<const ms::AdamTensor*>(tensors), n_tensors, lr, n_lr, 0, beta1, beta2, eps,
-                            step_dev, (hipStream_t)stream));
-    return MS_OK;
-}
-
-int ms_adam_step_dev_masked(const ms_adam_tensor* tensors, int32_t n_tensors, const double* lr, int32_t n_lr,
-                            const int64_t* step_dev, double beta1, double beta2, double eps, int32_t n_groups,
-                            const uint8_t* frozen_dev, void* stream) {
-    if (!tensors || !lr || !step_dev) return fail(MS_EINVAL, "NULL argument");
-    if (n_tensors < 1 || n_tensors > MS_ADAM_MAX_TENSORS) return fail(MS_EINVAL, "n_tensors must be in [1, %d]", MS_ADAM_MAX_TENSORS);
-    if (n_lr < 1 || n_lr > ms::kAdamMaxGroups) return fail(MS_EINVAL, "n_lr must be in [1, %d]", ms::kAdamMaxGroups);
+    if (!step_dev && step < 1) return fail(MS_EINVAL, "step must be >= 1");
     if (frozen_dev && n_groups < 1) return fail(MS_EINVAL, "ms_adam_step_dev_masked: n_groups must be >= 1");
     for (int i = 0; i < n_tensors; i++) {
         const ms_adam_tensor& t = tensors[i];
@@ -1310,17 +1242,43 @@ int ms_adam_step_dev_masked(const ms_adam_tensor* tensors, int32_t n_tensors, co
             return fail(MS_EINVAL, "ms_adam_step_dev_masked: tensor %d's %lld elements do not split into %d groups", i,
                         (long long)t.numel, n_groups);
     }
-    HIP_TRY(ms::launch_adam(reinterpret_cast<const ms::AdamTensor*>(tensors), n_tensors, lr, n_lr, 0, beta1, beta2, eps,
-                            step_dev, (hipStream_t)stream, frozen_dev, n_groups));
+    ms::AdamStep a{};
+    a.ts = reinterpret_cast<const ms::AdamTensor*>(tensors), a.n = n_tensors;
+    a.lr = lr, a.n_lr = n_lr, a.step = step, a.step_dev = step_dev;
+    a.beta1 = beta1, a.beta2 = beta2, a.eps = eps;
+    a.frozen = frozen_dev, a.n_groups = n_groups;
+    HIP_TRY(ms::launch_adam(a, (hipStream_t)stream));
     return MS_OK;
+}
+
+int ms_adam_step(const ms_adam_tensor* tensors, int32_t n_tensors, const double* lr, int32_t n_lr, int64_t step,
+                 double beta1, double beta2, double eps, void* stream) {
+    if (!tensors || !lr) return fail(MS_EINVAL, "NULL argument");
+    return adam_step(tensors, n_tensors, lr, n_lr, step, nullptr, beta1, beta2, eps, 0, nullptr, stream);
+}
+
+int ms_adam_step_dev(const ms_adam_tensor* tensors, int32_t n_tensors, const double* lr, int32_t n_lr,
+                     const int64_t* step_dev, double beta1, double beta2, double eps, void* stream) {
+    if (!tensors || !lr || !step_dev) return fail(MS_EINVAL, "NULL argument");
+    return adam_step(tensors, n_tensors, lr, n_lr, 0, step_dev, beta1, beta2, eps, 0, nullptr, stream);
+}
+
+int ms_adam_step_dev_masked(const ms_adam_tensor* tensors, int32_t n_tensors, const double* lr, int32_t n_lr,
+                            const int64_t* step_dev, double beta1, double beta2, double eps, int32_t n_groups,
+                            const uint8_t* frozen_dev, void* stream) {
+    if (!tensors || !lr || !step_dev) return fail(MS_EINVAL, "NULL argument");
+    return adam_step(tensors, n_tensors, lr, n_lr, 0, step_dev, beta1, beta2, eps, n_groups, frozen_dev, stream);
 }
 
 int ms_unit_returns(const void* rewards, int32_t rewards_i32, int32_t T, int64_t E, int32_t U,
                     const int32_t* unit_of_group, int32_t G, double gamma, float* out, void* stream) {
     if (!rewards || !unit_of_group || !out) return fail(MS_EINVAL, "NULL argument");
     if (T < 1 || E < 0 || U < 1 || G < 1) return fail(MS_EINVAL, "bad shape");
-    HIP_TRY(ms::launch_unit_returns(rewards, rewards_i32 ? 1 : 0, T, E, U, unit_of_group, G, gamma, out,
-                                    (hipStream_t)stream));
+    ms::UnitReturns a{};
+    a.rewards = rewards, a.is_i32 = rewards_i32 ? 1 : 0;
+    a.T = T, a.E = E, a.U = U, a.unit_of_group = unit_of_group, a.G = G;
+    a.gamma = gamma, a.out = out;
+    HIP_TRY(ms::launch_unit_returns(a, (hipStream_t)stream));
     return MS_OK;
 }
 

@@ -992,179 +992,159 @@ extern "C" int ms_probe_free_rounds(unsigned long long* out, int n_wgs) {
 }
 #endif
 
-// launch wrappers used by capi.cpp
+// launch wrappers used by capi.cpp (declared in ms_env_launch.h); the kernels take an EnvDev's fields one by one
 namespace ms {
-hipError_t launch_env_init(const Params& P, int64_t E, uint8_t* recs, uint32_t* mt, Liab* liab, uint64_t seed,
-                           hipStream_t s) {
+hipError_t launch_env_init(const EnvDev& d, uint64_t seed, hipStream_t s) {
+    const Params& P = d.P;
     // the seeding runs in the scratch, which k_env_init needs at MT-state size
     const size_t lds = (size_t)P.s_scratch + 4 * kMtN > (size_t)P.s_total ? (size_t)P.s_scratch + 4 * kMtN : P.s_total;
-    hipLaunchKernelGGL(k_env_init, dim3((unsigned)E), dim3(kWave), lds, s, P, recs, mt, liab, seed);
+    hipLaunchKernelGGL(k_env_init, dim3((unsigned)d.E), dim3(kWave), lds, s, P, d.recs, d.mt, d.liab, seed);
     return hipGetLastError();
 }
-hipError_t launch_env_reset(const Params& P, int64_t E, const uint8_t* recs, int8_t* a, int8_t* o, int8_t* u,
-                            int8_t* crow, int8_t* cown, hipStream_t s) {
-    hipLaunchKernelGGL(k_env_reset, dim3((unsigned)E), dim3(kWave), P.s_total, s, P, recs, a, o, u, crow, cown);
+hipError_t launch_env_reset(const EnvDev& d, const StepIO& io, hipStream_t s) {
+    hipLaunchKernelGGL(k_env_reset, dim3((unsigned)d.E), dim3(kWave), d.P.s_total, s, d.P, d.recs, io.obs_acc,
+                       io.obs_off, io.obs_auct, io.obs_crow, io.obs_cown);
     return hipGetLastError();
 }
 
 template <int LPE, class SH>
-static hipError_t launch_step_sh(const Params& P, int64_t E, uint8_t* recs, uint32_t* mt, Liab* liab, const StepIO& io,
-                                 const MixIO& mix, hipStream_t s) {
+static hipError_t launch_step_sh(const EnvDev& d, const StepIO& io, const MixIO& mix, hipStream_t s) {
     constexpr int G = kWave / LPE;
-    const int64_t blocks = (E + G - 1) / G;
-    const size_t lds = (size_t)P.s_total * G > 4 * kMtN ? (size_t)P.s_total * G : 4 * kMtN;  // >= one MT block
+    const int64_t blocks = (d.E + G - 1) / G;
+    const size_t lds = (size_t)d.P.s_total * G > 4 * kMtN ? (size_t)d.P.s_total * G : 4 * kMtN;  // >= one MT block
     const bool compact = io.obs_crow != nullptr || io.obs_cown != nullptr;
     // a mixed round (a mask, or the taken actions asked for) runs in the kernel of the optional features
     const bool mixed = mix.hc_mask != 0 || mix.acc_taken != nullptr || mix.off_taken != nullptr;
     const bool ext = io.act_acc == nullptr || io.metrics != nullptr || (compact && io.obs_acc != nullptr) || mixed;
     auto kern = ext ? k_env_step<LPE, true, false, DynShape>
                     : (compact ? k_env_step<LPE, false, true, SH> : k_env_step<LPE, false, false, SH>);
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(kWave), lds, s, P, E, recs, mt, liab, io, mix);
+    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(kWave), lds, s, d.P, d.E, d.recs, d.mt, d.liab, io, mix);
     return hipGetLastError();
 }
 
 // The BASELINE shapes (cfg2 4x4x3, cfg3 8x8x3, cfg4 16x16x3, cfg5 32x32x3, one new job per agent and
 // round) run the kernel compiled for their geometry; every other shape the generic one.
 template <int LPE>
-static hipError_t launch_step_t(const Params& P, int64_t E, uint8_t* recs, uint32_t* mt, Liab* liab, const StepIO& io,
-                                const MixIO& mix, hipStream_t s) {
+static hipError_t launch_step_t(const EnvDev& d, const StepIO& io, const MixIO& mix, hipStream_t s) {
 #ifndef MS_NO_FIXED_SHAPES
     if constexpr (LPE == 16) {
-        if (is_shape<8, 8, 3, 1>(P)) return launch_step_sh<LPE, FixShape<8, 8, 3, 1>>(P, E, recs, mt, liab, io, mix, s);
-        if (is_shape<16, 16, 3, 1>(P))
-            return launch_step_sh<LPE, FixShape<16, 16, 3, 1>>(P, E, recs, mt, liab, io, mix, s);
+        if (is_shape<8, 8, 3, 1>(d.P)) return launch_step_sh<LPE, FixShape<8, 8, 3, 1>>(d, io, mix, s);
+        if (is_shape<16, 16, 3, 1>(d.P)) return launch_step_sh<LPE, FixShape<16, 16, 3, 1>>(d, io, mix, s);
     }
     if constexpr (LPE == 32) {
-        if (is_shape<4, 4, 3, 1>(P)) return launch_step_sh<LPE, FixShape<4, 4, 3, 1>>(P, E, recs, mt, liab, io, mix, s);
-        if (is_shape<32, 32, 3, 1>(P))
-            return launch_step_sh<LPE, FixShape<32, 32, 3, 1>>(P, E, recs, mt, liab, io, mix, s);
+        if (is_shape<4, 4, 3, 1>(d.P)) return launch_step_sh<LPE, FixShape<4, 4, 3, 1>>(d, io, mix, s);
+        if (is_shape<32, 32, 3, 1>(d.P)) return launch_step_sh<LPE, FixShape<32, 32, 3, 1>>(d, io, mix, s);
     }
 #endif
-    return launch_step_sh<LPE, DynShape>(P, E, recs, mt, liab, io, mix, s);
+    return launch_step_sh<LPE, DynShape>(d, io, mix, s);
 }
 
-hipError_t launch_env_step(const Params& P, int64_t E, uint8_t* recs, uint32_t* mt, Liab* liab, const StepIO& io,
-                           const MixIO& mix, hipStream_t s) {
-    switch (lanes_per_env(P, E)) {
+hipError_t launch_env_step(const EnvDev& d, const StepIO& io, const MixIO& mix, hipStream_t s) {
+    switch (lanes_per_env(d.P, d.E)) {
 #if MS_MIN_LPE <= 8
-        case 8: return launch_step_t<8>(P, E, recs, mt, liab, io, mix, s);
+        case 8: return launch_step_t<8>(d, io, mix, s);
 #endif
-        case 16: return launch_step_t<16>(P, E, recs, mt, liab, io, mix, s);
-        case 32: return launch_step_t<32>(P, E, recs, mt, liab, io, mix, s);
-        default: return launch_step_t<64>(P, E, recs, mt, liab, io, mix, s);
+        case 16: return launch_step_t<16>(d, io, mix, s);
+        case 32: return launch_step_t<32>(d, io, mix, s);
+        default: return launch_step_t<64>(d, io, mix, s);
     }
 }
-hipError_t launch_env_auctioneer(const Params& P, int64_t E, uint8_t* recs, uint32_t* mt, int8_t* actions,
-                                 hipStream_t s) {
-    const size_t lds = (size_t)P.s_total > 4 * kMtN ? (size_t)P.s_total : 4 * kMtN;
-    hipLaunchKernelGGL(k_env_auctioneer, dim3((unsigned)E), dim3(kWave), lds, s, P, recs, mt, actions);
+hipError_t launch_env_auctioneer(const EnvDev& d, int8_t* actions, hipStream_t s) {
+    const size_t lds = (size_t)d.P.s_total > 4 * kMtN ? (size_t)d.P.s_total : 4 * kMtN;
+    hipLaunchKernelGGL(k_env_auctioneer, dim3((unsigned)d.E), dim3(kWave), lds, s, d.P, d.recs, d.mt, actions);
     return hipGetLastError();
 }
-hipError_t launch_env_randbelow(const Params& P, uint8_t* recs, uint32_t* mt, int64_t e, uint32_t n, uint32_t* out,
-                                hipStream_t s) {
-    hipLaunchKernelGGL(k_env_randbelow, dim3(1), dim3(kWave), 4 * kMtN, s, P, recs, mt, e, n, out);
+hipError_t launch_env_randbelow(const EnvDev& d, int64_t e, uint32_t n, uint32_t* out, hipStream_t s) {
+    hipLaunchKernelGGL(k_env_randbelow, dim3(1), dim3(kWave), 4 * kMtN, s, d.P, d.recs, d.mt, e, n, out);
     return hipGetLastError();
 }
 template <int LPE, class SH>
-static hipError_t launch_step_act_sh(const Params& P, int64_t E, uint8_t* recs, uint32_t* mt, Liab* liab,
-                                     const StepIO& io, const FusedAct& fa, uint64_t hc_mask, hipStream_t s) {
+static hipError_t launch_step_act_sh(const EnvDev& d, const StepIO& io, const FusedAct& fa, uint64_t hc_mask,
+                                     hipStream_t s) {
     constexpr int G = kWave / LPE;
-    const int64_t blocks = (E + G - 1) / G;
-    const size_t lds = (size_t)P.s_total * G > 4 * kMtN ? (size_t)P.s_total * G : 4 * kMtN;
+    const int64_t blocks = (d.E + G - 1) / G;
+    const size_t lds = (size_t)d.P.s_total * G > 4 * kMtN ? (size_t)d.P.s_total * G : 4 * kMtN;  // >= one MT block
     if (hc_mask) {  // a mixed population (ms_env_step_act_mixed); no mask: the plain kernels
         auto kern = io.metrics ? k_env_step_act_mixed<LPE, SH, true> : k_env_step_act_mixed<LPE, SH, false>;
-        hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(kWave), lds, s, P, E, recs, mt, liab, io, fa, hc_mask);
+        hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(kWave), lds, s, d.P, d.E, d.recs, d.mt, d.liab, io, fa,
+                           hc_mask);
         return hipGetLastError();
     }
     auto kern = io.metrics ? k_env_step_act<LPE, SH, true> : k_env_step_act<LPE, SH, false>;
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(kWave), lds, s, P, E, recs, mt, liab, io, fa);
+    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(kWave), lds, s, d.P, d.E, d.recs, d.mt, d.liab, io, fa);
     return hipGetLastError();
 }
-// hc_mask (here and in launch_env_rollout_act): the agents that play the rules in the rounds, 0 for none
-hipError_t launch_env_step_act(const Params& P, int64_t E, uint8_t* recs, uint32_t* mt, Liab* liab, const StepIO& io,
-                               const FusedAct& fa, uint64_t hc_mask, hipStream_t s) {
-    if (!env_step_act_supported(P, E) || io.act_acc == nullptr || io.obs_acc != nullptr) return hipErrorInvalidValue;
-    if (hc_mask && (io.act_off == nullptr || P.free_prices)) return hipErrorInvalidValue;
-    switch (lanes_per_env(P, E)) {
-        case 16: return launch_step_act_sh<16, DynShape>(P, E, recs, mt, liab, io, fa, hc_mask, s);
+hipError_t launch_env_step_act(const EnvDev& d, const StepIO& io, const FusedAct& fa, uint64_t hc_mask, hipStream_t s) {
+    if (!env_step_act_supported(d.P, d.E) || io.act_acc == nullptr || io.obs_acc != nullptr) return hipErrorInvalidValue;
+    if (hc_mask && (io.act_off == nullptr || d.P.free_prices)) return hipErrorInvalidValue;
+    switch (lanes_per_env(d.P, d.E)) {
+        case 16: return launch_step_act_sh<16, DynShape>(d, io, fa, hc_mask, s);
         case 32:
 #ifndef MS_NO_FIXED_SHAPES
-            if (is_shape<4, 4, 3, 1>(P))
-                return launch_step_act_sh<32, FixShape<4, 4, 3, 1>>(P, E, recs, mt, liab, io, fa, hc_mask, s);
+            if (is_shape<4, 4, 3, 1>(d.P)) return launch_step_act_sh<32, FixShape<4, 4, 3, 1>>(d, io, fa, hc_mask, s);
 #endif
-            return launch_step_act_sh<32, DynShape>(P, E, recs, mt, liab, io, fa, hc_mask, s);
-        default: return launch_step_act_sh<64, DynShape>(P, E, recs, mt, liab, io, fa, hc_mask, s);
+            return launch_step_act_sh<32, DynShape>(d, io, fa, hc_mask, s);
+        default: return launch_step_act_sh<64, DynShape>(d, io, fa, hc_mask, s);
     }
 }
 template <int LPE, class SH>
-static hipError_t launch_rollout_act_sh(const Params& P, int64_t E, uint8_t* recs, uint32_t* mt, Liab* liab,
-                                        const StepIO& io, const FusedAct& fa, const RoundStride& st, int n_rounds,
-                                        int act_last, uint64_t hc_mask, hipStream_t s) {
+static hipError_t launch_rollout_act_sh(const EnvDev& d, const RolloutArgs& A, uint64_t hc_mask, hipStream_t s) {
     constexpr int G = kWave / LPE;
-    const int64_t blocks = (E + G - 1) / G;
-    const size_t lds = (size_t)P.s_total * G > 4 * kMtN ? (size_t)P.s_total * G : 4 * kMtN;
-    const RolloutArgs A{P, E, recs, mt, liab, io, fa, st, n_rounds, act_last};
+    const int64_t blocks = (d.E + G - 1) / G;
+    const size_t lds = (size_t)d.P.s_total * G > 4 * kMtN ? (size_t)d.P.s_total * G : 4 * kMtN;  // >= one MT block
     if (hc_mask) {  // a mixed population (ms_env_rollout_act_mixed)
         const RolloutMixArgs M{A, hc_mask};
-        auto kern = io.metrics ? k_env_rollout_act_mixed<LPE, SH, true> : k_env_rollout_act_mixed<LPE, SH, false>;
+        auto kern = A.io.metrics ? k_env_rollout_act_mixed<LPE, SH, true> : k_env_rollout_act_mixed<LPE, SH, false>;
         hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(kWave), lds, s, M);
         return hipGetLastError();
     }
-    auto kern = io.metrics ? k_env_rollout_act<LPE, SH, true> : k_env_rollout_act<LPE, SH, false>;
+    auto kern = A.io.metrics ? k_env_rollout_act<LPE, SH, true> : k_env_rollout_act<LPE, SH, false>;
     hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(kWave), lds, s, A);
     return hipGetLastError();
 }
-hipError_t launch_env_rollout_act(const Params& P, int64_t E, uint8_t* recs, uint32_t* mt, Liab* liab,
-                                  const StepIO& io, const FusedAct& fa, const RoundStride& st, int n_rounds,
-                                  int act_last, uint64_t hc_mask, hipStream_t s) {
-    if (!env_step_act_supported(P, E) || io.act_acc == nullptr || io.obs_acc != nullptr || io.ev_acc != nullptr ||
+hipError_t launch_env_rollout_act(const EnvDev& d, const StepIO& io, const FusedAct& fa, const RoundStride& st,
+                                  int n_rounds, int act_last, uint64_t hc_mask, hipStream_t s) {
+    if (!env_step_act_supported(d.P, d.E) || io.act_acc == nullptr || io.obs_acc != nullptr || io.ev_acc != nullptr ||
         io.ev_term != nullptr || n_rounds < 1)
         return hipErrorInvalidValue;
-    if (hc_mask && (io.act_off == nullptr || P.free_prices)) return hipErrorInvalidValue;
-    switch (lanes_per_env(P, E)) {
-        case 16:
-            return launch_rollout_act_sh<16, DynShape>(P, E, recs, mt, liab, io, fa, st, n_rounds, act_last, hc_mask, s);
+    if (hc_mask && (io.act_off == nullptr || d.P.free_prices)) return hipErrorInvalidValue;
+    const RolloutArgs A{d.P, d.E, d.recs, d.mt, d.liab, io, fa, st, n_rounds, act_last};
+    switch (lanes_per_env(d.P, d.E)) {
+        case 16: return launch_rollout_act_sh<16, DynShape>(d, A, hc_mask, s);
         case 32:
 #ifndef MS_NO_FIXED_SHAPES
-            if (is_shape<4, 4, 3, 1>(P))
-                return launch_rollout_act_sh<32, FixShape<4, 4, 3, 1>>(P, E, recs, mt, liab, io, fa, st, n_rounds,
-                                                                       act_last, hc_mask, s);
+            if (is_shape<4, 4, 3, 1>(d.P)) return launch_rollout_act_sh<32, FixShape<4, 4, 3, 1>>(d, A, hc_mask, s);
 #endif
-            return launch_rollout_act_sh<32, DynShape>(P, E, recs, mt, liab, io, fa, st, n_rounds, act_last, hc_mask, s);
-        default:
-            return launch_rollout_act_sh<64, DynShape>(P, E, recs, mt, liab, io, fa, st, n_rounds, act_last, hc_mask, s);
+            return launch_rollout_act_sh<32, DynShape>(d, A, hc_mask, s);
+        default: return launch_rollout_act_sh<64, DynShape>(d, A, hc_mask, s);
     }
 }
 // RolloutFreeArgs::prio: the paced acting (wait after acting 9.0k -> 4.5k cycles, 47.07 -> 46.66 us per round against
 // waves 4.. at raised priority for the whole acting, profiles/r7; that 49.6 -> 49.0 against none, profiles/r7c)
 constexpr int kFreePrio = 4, kFreeSeparate = 1;
 template <class SH>
-static hipError_t launch_rollout_free_sh(const Params& P, int64_t E, uint8_t* recs, uint32_t* mt, Liab* liab,
-                                         const StepIO& io, const FusedActFree& fa, const RoundStrideFree& st,
-                                         int n_rounds, int act_last, hipStream_t s) {
-    const int64_t epb = (int64_t)kFreeEPW * P.N;
-    const int64_t blocks = (E + epb - 1) / epb;
+static hipError_t launch_rollout_free_sh(const RolloutFreeArgs& A, hipStream_t s) {
+    const int64_t epb = (int64_t)kFreeEPW * A.P.N;
+    const int64_t blocks = (A.E + epb - 1) / epb;
     // MS_FREE_STAGGER=0 (read at every launch; a captured launch keeps what it was captured with): the plain
     // kernel, the tests' reference. Otherwise the staggered one (17.26 -> 16.48 ms per cfg3 iteration,
     // profiles/r10a).
     const char* sv = getenv("MS_FREE_STAGGER");
     const bool stagger = !(sv && strcmp(sv, "0") == 0);
-    const RolloutFreeArgs A{P, E, recs, mt, liab, io, fa, st, n_rounds, act_last, kFreePrio, kFreeSeparate};
-    auto kern = stagger ? (io.metrics ? k_env_rollout_act_free<SH, true, true> : k_env_rollout_act_free<SH, false, true>)
-                        : (io.metrics ? k_env_rollout_act_free<SH, true> : k_env_rollout_act_free<SH, false>);
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(64 * P.N), (size_t)free_lds(P).total, s, A);
+    auto kern = stagger ? (A.io.metrics ? k_env_rollout_act_free<SH, true, true> : k_env_rollout_act_free<SH, false, true>)
+                        : (A.io.metrics ? k_env_rollout_act_free<SH, true> : k_env_rollout_act_free<SH, false>);
+    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(64 * A.P.N), (size_t)free_lds(A.P).total, s, A);
     return hipGetLastError();
 }
-hipError_t launch_env_rollout_act_free(const Params& P, int64_t E, uint8_t* recs, uint32_t* mt, Liab* liab,
-                                       const StepIO& io, const FusedActFree& fa, const RoundStrideFree& st,
-                                       int n_rounds, int act_last, hipStream_t s) {
-    if (!env_rollout_free_supported(P) || io.act_acc == nullptr || io.obs_acc != nullptr || io.ev_acc != nullptr ||
+hipError_t launch_env_rollout_act_free(const EnvDev& d, const StepIO& io, const FusedActFree& fa,
+                                       const RoundStrideFree& st, int n_rounds, int act_last, hipStream_t s) {
+    if (!env_rollout_free_supported(d.P) || io.act_acc == nullptr || io.obs_acc != nullptr || io.ev_acc != nullptr ||
         io.ev_term != nullptr || n_rounds < 1)
         return hipErrorInvalidValue;
+    const RolloutFreeArgs A{d.P, d.E, d.recs, d.mt, d.liab, io, fa, st, n_rounds, act_last, kFreePrio, kFreeSeparate};
 #ifndef MS_NO_FIXED_SHAPES
-    if (is_shape<8, 8, 3, 1>(P))
-        return launch_rollout_free_sh<FixShape<8, 8, 3, 1>>(P, E, recs, mt, liab, io, fa, st, n_rounds, act_last, s);
+    if (is_shape<8, 8, 3, 1>(d.P)) return launch_rollout_free_sh<FixShape<8, 8, 3, 1>>(A, s);
 #endif
-    return launch_rollout_free_sh<DynShape>(P, E, recs, mt, liab, io, fa, st, n_rounds, act_last, s);
+    return launch_rollout_free_sh<DynShape>(A, s);
 }
 }  // namespace ms

@@ -21,26 +21,11 @@
 #include <math.h>
 
 #include "../../include/marlsched.h"
-#include "ms_act_kernels.h"  // the launch-shape helpers shared with the sampling kernels
+#include "ms_act_kernels.h"  // the launch-shape helpers shared with the sampling kernels; GreedyArgs: ms_act_args.h
 
 #pragma clang fp contract(fast)  // (build.sh: -ffp-contract=fast for this file)
 
 namespace ms {
-
-struct GreedyArgs {
-    ms_mlp_params n1, n2;  // n2: the price chooser (NT2 > 0 only)
-    const int8_t* obs;     // [E][U][stride], or with owner the core rows [E][C][stride]
-    const int8_t* owner;   // [E][C] or NULL: row (e, u = a*C + c) is core row (e, c) if owner[e][c] == a + 1
-    const int8_t* common;  // [stride] or NULL
-    int stride, U, S, n_cores;
-    int E, n_items;
-    int tiles_per_wave, items_per_wave, waves_per_group;
-    int8_t* action;
-    float* logprob;        // or NULL
-    int8_t* price_state;   // [E*U][4]
-    int8_t* price_action;
-    int8_t* env_price;
-};
 
 constexpr int kGreedySeg = 512;  // most items per wave of k_greedy_common = capacity of its LDS row list
 
@@ -362,8 +347,8 @@ static hipError_t dispatch_greedy_s(GreedyArgs& a, hipStream_t st) {
     return hipErrorInvalidValue;
 }
 
-static hipError_t dispatch_greedy(GreedyArgs& a, hipStream_t st) {
-    if (!greedy_fits(a)) return hipErrorInvalidValue;
+hipError_t dispatch_greedy(GreedyArgs& a, hipStream_t st) {
+    if (a.E < 1 || (long long)a.E * a.U > 0x7fffffffll || !greedy_fits(a)) return hipErrorInvalidValue;
     if (a.n2.n_groups > 0 &&
         (a.n2.in_dim != 4 || a.n2.hidden != 16 || a.n2.n_actions < 1 || a.n2.n_actions > 128 ||
          a.n2.n_groups != a.n1.n_groups || 2 * a.n_cores + 2 > a.stride || a.n1.n_actions > a.n_cores + 1))
@@ -378,55 +363,16 @@ static hipError_t dispatch_greedy(GreedyArgs& a, hipStream_t st) {
     return hipErrorInvalidValue;
 }
 
-static GreedyArgs greedy_args(const ms_mlp_params* p, const int8_t* obs, int stride, int64_t E, int U, int S,
-                              int8_t* action, float* logprob) {
-    GreedyArgs a{};
-    a.n1 = *p;
-    a.n2.n_groups = 0;
-    a.obs = obs;
-    a.stride = stride;
-    a.U = U;
-    a.S = S;
-    a.E = (int)E;
-    a.n_items = (int)(E * S);
-    a.action = action;
-    a.logprob = logprob;
-    return a;
-}
-
-hipError_t launch_policy_act_greedy(const ms_mlp_params* p, const int8_t* obs, int stride, int64_t E, int U, int S,
-                                    const int8_t* common, int8_t* action, float* logprob, hipStream_t st) {
-    if (E < 1 || E * (int64_t)U > 0x7fffffffll) return hipErrorInvalidValue;
-    GreedyArgs a = greedy_args(p, obs, stride, E, U, S, action, logprob);
-    a.common = common;
-    return dispatch_greedy(a, st);
-}
-
 // both halves of a round in one launch where their shapes have a paired kernel (the shapes k_act_pair is
 // built for: cfg2, cfg3, cfg4), else the two launches in order
-hipError_t launch_act_round_greedy(const ms_mlp_params* core, const ms_mlp_params* price, const int8_t* off_obs,
-                                   int off_stride, int off_U, int off_S, const ms_mlp_params* acc,
-                                   const int8_t* core_rows, const int8_t* core_owner, int acc_stride, int acc_U,
-                                   int acc_S, int n_cores, const int8_t* common, int64_t E, int8_t* core_action,
-                                   int8_t* price_state, int8_t* price_action, int8_t* env_price, int8_t* acc_action,
-                                   hipStream_t st) {
-    if (E < 1 || E * (int64_t)off_U > 0x7fffffffll || E * (int64_t)acc_U > 0x7fffffffll) return hipErrorInvalidValue;
-    GreedyArgs o = greedy_args(core, off_obs, off_stride, E, off_U, off_S, core_action, nullptr);
-    o.n_cores = n_cores;
-    if (price) {
-        o.n2 = *price;
-        o.price_state = price_state;
-        o.price_action = price_action;
-        o.env_price = env_price;
-    }
-    GreedyArgs c = greedy_args(acc, core_rows, acc_stride, E, acc_U, acc_S, acc_action, nullptr);
-    c.common = common;
-    c.owner = core_owner;
-    c.n_cores = n_cores;
-    if (!common || !core_owner) return hipErrorInvalidValue;
-    const int s1a = s1_bucket(off_stride), nta = nt_bucket(core->n_actions);
-    const int nt2 = price ? nt_bucket(price->n_actions) : 0;
-    const int s1b = s1_bucket(acc_stride), ntb = nt_bucket(acc->n_actions);
+hipError_t launch_act_round_greedy(GreedyArgs& o, GreedyArgs& c, hipStream_t st) {
+    if (o.E < 1 || c.E != o.E || (long long)o.E * o.U > 0x7fffffffll || (long long)c.E * c.U > 0x7fffffffll)
+        return hipErrorInvalidValue;
+    if (!c.common || !c.owner) return hipErrorInvalidValue;
+    const bool price = o.n2.n_groups > 0;
+    const int s1a = s1_bucket(o.stride), nta = nt_bucket(o.n1.n_actions);
+    const int nt2 = price ? nt_bucket(o.n2.n_actions) : 0;
+    const int s1b = s1_bucket(c.stride), ntb = nt_bucket(c.n1.n_actions);
     const int shape = s1a == 1 && nta == 1 && nt2 == 0 && s1b == 1 && ntb == 1   ? 2
                       : s1a == 1 && nta == 1 && nt2 == 1 && s1b == 2 && ntb <= 2 ? 3
                       : s1a == 2 && nta <= 2 && nt2 == 1 && s1b == 4 && ntb <= 4 ? 4
@@ -436,9 +382,9 @@ hipError_t launch_act_round_greedy(const ms_mlp_params* core, const ms_mlp_param
         return e != hipSuccess ? e : dispatch_greedy(c, st);
     }
     // the checks dispatch_greedy makes for each half
-    if (!greedy_fits(o) || !greedy_fits(c) || n_cores < 1 || acc_U % n_cores != 0) return hipErrorInvalidValue;
-    if (price && (price->in_dim != 4 || price->hidden != 16 || price->n_actions < 1 ||
-                  price->n_groups != core->n_groups || 2 * n_cores + 2 > off_stride || core->n_actions > n_cores + 1))
+    if (!greedy_fits(o) || !greedy_fits(c) || c.n_cores < 1 || c.U % c.n_cores != 0) return hipErrorInvalidValue;
+    if (price && (o.n2.in_dim != 4 || o.n2.hidden != 16 || o.n2.n_actions < 1 || o.n2.n_groups != o.n1.n_groups ||
+                  2 * o.n_cores + 2 > o.stride || o.n1.n_actions > o.n_cores + 1))
         return hipErrorInvalidValue;
     const unsigned ob = greedy_tile_blocks(o, kGreedyWaves), cb = greedy_common_blocks(c, kGreedyCommonWaves);
     if (shape == 2)

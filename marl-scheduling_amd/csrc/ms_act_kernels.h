@@ -1,8 +1,8 @@
 // ms_act_kernels.h — what the acting translation units share (policy_kernels.hip, act_pair_kernels.hip,
-// greedy_kernels.hip): the sampling kernels' arguments (ActArgs), their two device bodies (act_tiles:
-// k_act's; act_common_rows: k_act_common's; k_act_pair runs one of each) and the host-side launch
-// plumbing (shape buckets, wave splits, size checks, argument builders). The kernels themselves are
-// defined once, each in the unit whose compiler flags suit it (build.sh).
+// greedy_kernels.hip): the sampling kernels' two device bodies (act_tiles: k_act's; act_common_rows:
+// k_act_common's; k_act_pair runs one of each) and the host-side launch plumbing (shape buckets, wave
+// splits, size checks). The kernels themselves are defined once, each in the unit whose compiler flags
+// suit it (build.sh); their arguments and launchers are declared in ms_act_args.h.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -11,6 +11,7 @@
 #include "../../include/marlsched.h"
 #include "ms_common.h"
 #include "ms_act.h"
+#include "ms_act_args.h"
 
 #pragma clang fp contract(fast)  // as ms_act.h (build.sh: -ffp-contract=fast for the acting units)
 
@@ -48,34 +49,6 @@ static __device__ unsigned long long g_act_waves[2][kActProbeWaves];
 #define MS_APROBE_BEGIN
 #define MS_APROBE_END(half)
 #endif
-
-struct ActArgs {
-    ms_mlp_params n1, n2;  // n2 used only with a price net (NT2 > 0)
-    const int8_t* obs;
-    int stride, U, S, n_cores;
-    int E, n_items;
-    int tiles_per_wave, waves_per_group;
-    uint64_t seed, offset;
-    const uint64_t* offset_dev;
-    const float* uniforms;  // [2][E*U] or NULL
-    int8_t* action;
-    float* logprob;
-    int8_t* price_state;   // [E*U][4] (pus = 0) or unit-major: row (e, u) at u * pus + e
-    int8_t* price_action;
-    float* price_logprob;
-    int64_t pus;           // unit stride (rows) of the price chooser's outputs; 0: [E][U]
-    int8_t* env_price;
-    const int8_t* common;  // [stride] or NULL (k_act_common)
-    int items_per_wave;    // k_act_common
-    // compact acceptor observations (k_act_common<.., OWN>): obs = core rows [E][C][stride], owner
-    // [E][C]; row (e, u = a*C + c) is core row (e, c) if owner[e][c] == a + 1, else the common row
-    const int8_t* owner;
-    // price chooser sampling table (ms_price_table): ptab [G][pkeys][kPriceTW], pdigit [4][256]
-    // (key offset of byte value v at position p, index v + 128; -1: not tabulated); NULL: computed
-    const float* ptab;
-    const int16_t* pdigit;
-    int pkeys;
-};
 
 // floats per price-table entry: running sums and log-probs of 16 * NT2 actions, S, last nonzero
 template <int NT2>
@@ -698,56 +671,5 @@ static bool act_tiles_fits(const ActArgs& a) {
     return rows < (1ll << 24) && rows * a.stride <= 0x7fffffffll && 4 * pc <= 0x7fffffffll &&
            (long long)a.pkeys * PriceTW<8>::v * 4 <= 0x7fffffffll;
 }
-
-// the fields every sampling launch sets: the net, its rows, the core outputs and the random stream
-static ActArgs act_args(const ms_mlp_params* p, const int8_t* obs, int stride, int64_t E, int U, int S, uint64_t seed,
-                        uint64_t offset, const uint64_t* offset_dev, const float* uniforms, int8_t* action,
-                        float* logprob) {
-    ActArgs a{};
-    a.n1 = *p;
-    a.n2.n_groups = 0;
-    a.obs = obs;
-    a.stride = stride;
-    a.U = U;
-    a.S = S;
-    a.E = (int)E;
-    a.n_items = (int)(E * S);
-    a.seed = seed;
-    a.offset = offset;
-    a.offset_dev = offset_dev;
-    a.uniforms = uniforms;
-    a.action = action;
-    a.logprob = logprob;
-    return a;
-}
-
-static ActArgs compact_args(const ms_mlp_params* p, const int8_t* core_rows, const int8_t* core_owner, int stride,
-                            int64_t E, int U, int S, int n_cores, const int8_t* common, uint64_t seed, uint64_t offset,
-                            const uint64_t* offset_dev, const float* uniforms, int8_t* action, float* logprob) {
-    ActArgs a = act_args(p, core_rows, stride, E, U, S, seed, offset, offset_dev, uniforms, action, logprob);
-    a.common = common;
-    a.owner = core_owner;
-    a.n_cores = n_cores;
-    return a;
-}
-
-static ActArgs offer_free_args(const ms_mlp_params* core, const ms_mlp_params* price, const int8_t* obs, int stride,
-                               int64_t E, int U, int S, int n_cores, uint64_t seed, uint64_t offset,
-                               const uint64_t* offset_dev, const float* uniforms, int8_t* core_action,
-                               float* core_logprob, int8_t* price_state, int8_t* price_action, float* price_logprob,
-                               int8_t* env_price, int64_t pus) {
-    ActArgs a = act_args(core, obs, stride, E, U, S, seed, offset, offset_dev, uniforms, core_action, core_logprob);
-    a.n2 = *price;
-    a.n_cores = n_cores;
-    a.price_state = price_state;
-    a.price_action = price_action;
-    a.price_logprob = price_logprob;
-    a.env_price = env_price;
-    a.pus = pus;
-    return a;
-}
-
-// one launch of k_act or k_act_common, whichever a's shape and common row ask for (policy_kernels.hip)
-hipError_t dispatch_act(ActArgs& a, hipStream_t st);
 
 }  // namespace ms

@@ -1,7 +1,9 @@
-// ms_bdqn.h — launch arguments of the Branching DQN acting kernels (bdqn_kernels.hip), shared with capi.cpp.
+// ms_bdqn.h — launch arguments and launchers of the Branching DQN kernels (bdqn_kernels.hip,
+// bdqn_update_kernels.hip), shared with capi.cpp.
 #pragma once
 
 #include <stddef.h>
+#include <hip/hip_runtime.h>
 #include <stdint.h>
 
 namespace ms {
@@ -81,5 +83,19 @@ struct BdqnUpd {
     BdqnGrads g;
 };
 constexpr int kUpdMaxHeadRows = 5440;  // Mp * 3 floats of one row's head outputs in 64 KB of LDS
+
+
+// ---- bdqn_kernels.hip
+// layer 1's weights as three bf16 terms per segment of seg inputs, padded to Dp (once per weight update)
+hipError_t launch_bdqn_w1split(const float* w1, int seg, int segs, int Dp, uint16_t* out, hipStream_t st);
+// the foreign rows' layer-1 sums cF and the all-foreign pre-activation base (once per weight update)
+hipError_t launch_bdqn_l1_base(const float* w1, const float* b1, int D, int C, float* cF, float* base, hipStream_t st);
+// layer 1 of aggregated rows from the compact observations (core rows + owners)
+hipError_t launch_bdqn_l1_compact(const BdqnL1Compact& p, hipStream_t st);
+// the branching net's epsilon-greedy actions
+hipError_t launch_bdqn_act(const BdqnAct& p, hipStream_t st);
+// ---- bdqn_update_kernels.hip
+// one learner step's gradients (forward of q(s), q(s'), target(s'), loss, backward) into p.g
+hipError_t launch_bdqn_update(const BdqnUpd& p, hipStream_t st);
 
 }  // namespace ms

@@ -1,6 +1,7 @@
-// ms_dqn.h — launch arguments of the DQN kernels (dqn_kernels.hip), shared with capi.cpp.
+// ms_dqn.h — launch arguments and launchers of the DQN kernels (dqn_kernels.hip), shared with capi.cpp.
 #pragma once
 
+#include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
 
@@ -47,5 +48,11 @@ struct DqnReduceArgs {
 
 size_t dqn_act_lds(const QArgs& q);
 size_t dqn_grad_lds(const QArgs& q, int xpitch);
+
+
+// epsilon-greedy actions of every unit of every replica (and the argmax, if asked for)
+hipError_t launch_dqn_act(const DqnActArgs& a, hipStream_t s);
+// the sampled transitions' per-block gradient partials, then their clipped sum into the gradient tensors
+hipError_t launch_dqn_grad(const DqnGradArgs& a, const DqnReduceArgs& r, hipStream_t s);
 
 }  // namespace ms

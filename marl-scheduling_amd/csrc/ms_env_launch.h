@@ -1,7 +1,10 @@
-// ms_env_launch.h — the host-side choices more than one env launcher makes (env_kernels.hip,
-// acc_fill_kernels.hip) and capi.cpp asks about: the lane-group width of a launch, the shapes with a kernel
-// compiled for their geometry, and the shapes the fused step + act kernels and the free-price rollout take.
+// ms_env_launch.h — the env launchers (env_kernels.hip, acc_fill_kernels.hip) as capi.cpp calls them, and the
+// host-side choices more than one of them makes and capi.cpp asks about: the lane-group width of a launch, the
+// shapes with a kernel compiled for their geometry, and the shapes the fused step + act kernels and the
+// free-price rollout take.
 #pragma once
+
+#include <hip/hip_runtime.h>
 
 #include "ms_layout.h"
 
@@ -46,5 +49,32 @@ inline bool env_step_act_supported(const Params& P, int64_t E) {
 inline bool env_rollout_free_supported(const Params& P) {
     return P.free_prices && free_rollout_shape_ok(P) && free_rollout_lds_ok(P);
 }
+
+// ---- env_kernels.hip (the kernels take d's fields one by one)
+// seeds every replica's MT19937 from seed (CPython's init_by_array) and spawns its first jobs
+hipError_t launch_env_init(const EnvDev& d, uint64_t seed, hipStream_t s);
+// the observations of the current state into io.obs_* (each may be NULL); nothing else of io is read
+hipError_t launch_env_reset(const EnvDev& d, const StepIO& io, hipStream_t s);
+// one round; mix: the agents that play the rules and where the actions the round used go (MixIO{}: none)
+hipError_t launch_env_step(const EnvDev& d, const StepIO& io, const MixIO& mix, hipStream_t s);
+// one round and the next round's acting (fixed prices); hc_mask, here and below: the agents that play the rules
+hipError_t launch_env_step_act(const EnvDev& d, const StepIO& io, const FusedAct& fa, uint64_t hc_mask, hipStream_t s);
+// n_rounds of launch_env_step_act in one launch, round t's arrays st's strides past round 0's
+hipError_t launch_env_rollout_act(const EnvDev& d, const StepIO& io, const FusedAct& fa, const RoundStride& st,
+                                  int n_rounds, int act_last, uint64_t hc_mask, hipStream_t s);
+// the same for a locally shared free-price env; leaves the acceptor items launch_env_fill_common samples
+hipError_t launch_env_rollout_act_free(const EnvDev& d, const StepIO& io, const FusedActFree& fa,
+                                       const RoundStrideFree& st, int n_rounds, int act_last, hipStream_t s);
+// random.randrange(n) of replica e's generator into *out (device word)
+hipError_t launch_env_randbelow(const EnvDev& d, int64_t e, uint32_t n, uint32_t* out, hipStream_t s);
+// the hard-coded auctioneer's actions [E][C] of the current state
+hipError_t launch_env_auctioneer(const EnvDev& d, int8_t* actions, hipStream_t s);
+
+// ---- acc_fill_kernels.hip
+// an acceptor act fragment block's common-row tables: agent 0's, and the dwords between two agents' tables
+void acc_common_tables(const void* act_frag, const uint32_t** tab0, int* group_dwords);
+// the acceptor items launch_env_rollout_act_free leaves, with its arguments (of io only obs_cown is read)
+hipError_t launch_env_fill_common(const Params& P, int64_t E, const StepIO& io, const FusedActFree& fa,
+                                  const RoundStrideFree& st, int n_rounds, int act_last, hipStream_t s);
 
 }  // namespace ms

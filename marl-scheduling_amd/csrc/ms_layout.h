@@ -139,6 +139,16 @@ struct Params : Geom {
     float net_zero;
 };
 
+// an env's device state: E replicas' records, MT19937 blocks (two per replica) and liability chains (what the env
+// launchers take, ms_env_launch.h; ms_env in capi.cpp is one of these and the host's bookkeeping)
+struct EnvDev {
+    Params P;
+    int64_t E;
+    uint8_t* recs;
+    uint32_t* mt;
+    Liab* liab;
+};
+
 // device pointers of one ms_env_step call
 struct StepIO {
     const int8_t* act_acc;

@@ -1,7 +1,8 @@
-// ms_ppo.h — launch arguments of the fused PPO gradient kernel (ppo_kernels.hip),
+// ms_ppo.h — launch arguments and launchers of the fused PPO gradient and Adam kernels (ppo_kernels.hip),
 // shared with the host ABI (capi.cpp).
 #pragma once
 
+#include <hip/hip_runtime.h>
 #include <stdint.h>
 
 namespace ms {
@@ -102,6 +103,20 @@ struct AdamTensor {  // layout of ms_adam_tensor
     int32_t lr_group;
 };
 
+// one Adam step over n tensors (ms_adam_step*): the step count on the host (step >= 1) or, for graph replays, on
+// the device (step_dev, step ignored); frozen (device, [n_groups] bytes; NULL: none): the groups, of every tensor's
+// n_groups equal parts, that the step leaves untouched
+struct AdamStep {
+    const AdamTensor* ts;  // [n]
+    int n, n_lr;
+    const double* lr;  // [n_lr] (host), indexed by AdamTensor::lr_group
+    int64_t step;
+    const int64_t* step_dev;
+    double beta1, beta2, eps;
+    const uint8_t* frozen;
+    int n_groups;
+};
+
 struct GradOut {
     float *w1, *b1, *w2, *b2, *w3, *b3, *cw1, *cb1, *cw2, *cb2, *cw3, *cb3, *loss;
 };
@@ -132,5 +147,16 @@ inline POff poff(int D, int A) {
     o.total = o.loss + 3;
     return o;
 }
+
+
+// the launchers of ppo_kernels.hip
+// the clipped-surrogate, value and entropy gradients of every group: per-block partials, then their sum into go
+hipError_t launch_ppo_grad(const PpoArgs& a, const GradOut& go, hipStream_t st);
+// floats of one group's gradient vector (poff(D, A).total)
+int ppo_param_count(int D, int A);
+// partial vectors per group that launch_ppo_grad writes (the keyed path adds its slot blocks)
+int ppo_partial_rows(int n_chunks, bool keyed);
+// torch.optim.Adam's foreach step over a.ts in one launch
+hipError_t launch_adam(const AdamStep& a, hipStream_t st);
 
 }  // namespace ms

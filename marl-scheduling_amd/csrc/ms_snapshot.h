@@ -19,6 +19,9 @@
 #include <stdint.h>
 
 #include "ms_layout.h"
+#ifdef __HIPCC__
+#include <hip/hip_runtime.h>
+#endif
 
 namespace ms {
 
@@ -152,5 +155,16 @@ struct SnapArgs {
     SnapLayout lay;
     int64_t E, n_liab;
 };
+
+
+#ifdef __HIPCC__  // the launchers of snapshot_kernels.hip (everything above needs no HIP: tests/snapshot_check.cpp)
+// The whole pack, or the count alone (a.buf NULL); *total (host-coherent) = n_liab once the stream has run
+hipError_t launch_snap_pack(const Params& P, const SnapArgs& a, const SnapHeader& h, const uint8_t* cfg_bytes,
+                            uint64_t* total, hipStream_t st);
+// the snapshot's sections back into the env's arrays (validated first: launch_snap_validate)
+hipError_t launch_snap_unpack(const Params& P, const SnapArgs& a, hipStream_t st);
+// result[0]: the first failing (replica << 24 | failure), ~0 for none; result[1]: the OR of the records' flags
+hipError_t launch_snap_validate(const Params& P, const SnapArgs& a, unsigned long long* result, hipStream_t st);
+#endif
 
 }  // namespace ms

@@ -1,9 +1,10 @@
-// ms_wide.h — launch arguments of the wide-net PPO kernels (wide_kernels.hip), shared with capi.cpp.
+// ms_wide.h — launch arguments and launchers of the wide-net PPO kernels (wide_kernels.hip), shared with capi.cpp.
 // "Wide" nets are the aggregated agents' ActorCritics (PPOmodules.py:177-232): 32 or 64 hidden units
 // and (O+1)^C, (C+1)^L or their product actions, one net per agent (group).
 #pragma once
 
 #include <stddef.h>
+#include <hip/hip_runtime.h>
 #include <stdint.h>
 
 namespace ms {
@@ -80,5 +81,11 @@ struct WideReduce {
     float* loss;        // [G][3]
     float inv_R;
 };
+
+
+// the wide net's sampled actions, log-probs and values
+hipError_t launch_wide_act(const WideAct& p, hipStream_t st);
+// rows -> split partials -> gradient tensors (three launches on one stream)
+hipError_t launch_wide_grad(const WideRows& rows, const WideGrads& gp, const WideReduce& rp, hipStream_t st);
 
 }  // namespace ms

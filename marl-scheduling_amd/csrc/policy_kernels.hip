@@ -90,7 +90,9 @@ static hipError_t dispatch_act_s(ActArgs& a, hipStream_t st) {
 }
 
 hipError_t dispatch_act(ActArgs& a, hipStream_t st) {
-    if (a.n2.n_groups > 0 && a.n2.in_dim != 4) return hipErrorInvalidValue;
+    if (a.E < 1 || (a.n2.n_groups > 0 && a.n2.in_dim != 4)) return hipErrorInvalidValue;
+    // compact rows are k_act_common's alone: they need the common row, and the units split into agents' cores
+    if (a.owner && (!a.common || a.stride < 16 || a.n_cores < 1 || a.U % a.n_cores != 0)) return hipErrorInvalidValue;
     switch (s1_bucket(a.stride)) {
         case 1: return dispatch_act_s<1>(a, st);
         case 2: return dispatch_act_s<2>(a, st);
@@ -98,34 +100,6 @@ hipError_t dispatch_act(ActArgs& a, hipStream_t st) {
         case 8: return dispatch_act_s<8>(a, st);
     }
     return hipErrorInvalidValue;
-}
-
-hipError_t launch_policy_act(const ms_mlp_params* p, const int8_t* obs, int stride, int64_t E, int U, int S,
-                             const int8_t* common, uint64_t seed, uint64_t offset, const uint64_t* offset_dev,
-                             const float* uniforms, int8_t* action, float* logprob, hipStream_t st) {
-    ActArgs a = act_args(p, obs, stride, E, U, S, seed, offset, offset_dev, uniforms, action, logprob);
-    a.common = common;
-    return dispatch_act(a, st);
-}
-
-hipError_t launch_policy_act_compact(const ms_mlp_params* p, const int8_t* core_rows, const int8_t* core_owner,
-                                     int stride, int64_t E, int U, int S, int n_cores, const int8_t* common,
-                                     uint64_t seed, uint64_t offset, const uint64_t* offset_dev, const float* uniforms,
-                                     int8_t* action, float* logprob, hipStream_t st) {
-    if (!common || stride < 16 || n_cores < 1 || U % n_cores != 0) return hipErrorInvalidValue;
-    ActArgs a = compact_args(p, core_rows, core_owner, stride, E, U, S, n_cores, common, seed, offset, offset_dev,
-                             uniforms, action, logprob);
-    return dispatch_act(a, st);
-}
-
-hipError_t launch_offer_act_free(const ms_mlp_params* core, const ms_mlp_params* price, const int8_t* obs, int stride,
-                                 int64_t E, int U, int S, int n_cores, uint64_t seed, uint64_t offset,
-                                 const uint64_t* offset_dev, const float* uniforms, int8_t* core_action,
-                                 float* core_logprob, int8_t* price_state, int8_t* price_action, float* price_logprob,
-                                 int8_t* env_price, int64_t pus, hipStream_t st) {
-    ActArgs a = offer_free_args(core, price, obs, stride, E, U, S, n_cores, seed, offset, offset_dev, uniforms,
-                                core_action, core_logprob, price_state, price_action, price_logprob, env_price, pus);
-    return dispatch_act(a, st);
 }
 
 // ms_act_prepare: one wave per group writes each lane's fragment (what the acting waves would derive:

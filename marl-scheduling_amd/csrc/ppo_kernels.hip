@@ -1995,40 +1995,38 @@ __global__ void __launch_bounds__(256) k_adam_masked(AdamArgs a, const uint8_t* 
     }
 }
 
-hipError_t launch_adam(const AdamTensor* ts, int n, const double* lr, int n_lr, int64_t step, double beta1,
-                       double beta2, double eps, const int64_t* step_dev, hipStream_t st, const uint8_t* frozen,
-                       int n_groups) {
-    // frozen (device, [n_groups] bytes; NULL: none): the groups the step leaves untouched (k_adam_masked)
-    if (n < 1 || n > kAdamMaxTensors || n_lr < 1 || n_lr > kAdamMaxGroups || (step < 1 && !step_dev))
+hipError_t launch_adam(const AdamStep& p, hipStream_t st) {
+    if (p.n < 1 || p.n > kAdamMaxTensors || p.n_lr < 1 || p.n_lr > kAdamMaxGroups || (p.step < 1 && !p.step_dev))
         return hipErrorInvalidValue;
-    if (frozen && n_groups < 1) return hipErrorInvalidValue;
-    if (step_dev) step = 1;  // the host-side corrections are unused
+    if (p.frozen && p.n_groups < 1) return hipErrorInvalidValue;
+    const int64_t step = p.step_dev ? 1 : p.step;  // (a device step: the host-side corrections are unused)
     AdamArgs a{};
-    a.step_dev = step_dev;
-    a.beta1d = beta1;
-    a.beta2d = beta2;
-    for (int k = 0; k < n_lr; k++) a.lr[k] = lr[k];
+    a.step_dev = p.step_dev;
+    a.beta1d = p.beta1;
+    a.beta2d = p.beta2;
+    for (int k = 0; k < p.n_lr; k++) a.lr[k] = p.lr[k];
     int64_t mx = 1;
-    for (int i = 0; i < n; i++) {
-        if (ts[i].lr_group < 0 || ts[i].lr_group >= n_lr) return hipErrorInvalidValue;
-        if (frozen && (ts[i].numel < n_groups || ts[i].numel % n_groups != 0)) return hipErrorInvalidValue;
-        a.t[i] = ts[i];
-        mx = ts[i].numel > mx ? ts[i].numel : mx;
+    for (int i = 0; i < p.n; i++) {
+        const AdamTensor& t = p.ts[i];
+        if (t.lr_group < 0 || t.lr_group >= p.n_lr) return hipErrorInvalidValue;
+        if (p.frozen && (t.numel < p.n_groups || t.numel % p.n_groups != 0)) return hipErrorInvalidValue;
+        a.t[i] = t;
+        mx = t.numel > mx ? t.numel : mx;
     }
     // the scalars as torch computes them (Python floats) and passes them to the f32 foreach ops
-    const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
-    a.w1 = (float)(1.0 - beta1);
-    a.beta2 = (float)beta2;
-    a.one_m_beta2 = (float)(1.0 - beta2);
-    a.eps = (float)eps;
-    for (int k = 0; k < n_lr; k++) a.neg_step[k] = (float)((lr[k] / bc1) * -1.0);
+    const double bc1 = 1.0 - pow(p.beta1, (double)step), bc2 = 1.0 - pow(p.beta2, (double)step);
+    a.w1 = (float)(1.0 - p.beta1);
+    a.beta2 = (float)p.beta2;
+    a.one_m_beta2 = (float)(1.0 - p.beta2);
+    a.eps = (float)p.eps;
+    for (int k = 0; k < p.n_lr; k++) a.neg_step[k] = (float)((p.lr[k] / bc1) * -1.0);
     a.bc2_sqrt = (float)sqrt(bc2);
     int64_t bx = (mx + 255) / 256;
     bx = bx > 1024 ? 1024 : bx;
-    if (frozen)
-        hipLaunchKernelGGL(k_adam_masked, dim3((unsigned)bx, (unsigned)n), dim3(256), 0, st, a, frozen, n_groups);
+    if (p.frozen)
+        hipLaunchKernelGGL(k_adam_masked, dim3((unsigned)bx, (unsigned)p.n), dim3(256), 0, st, a, p.frozen, p.n_groups);
     else
-        hipLaunchKernelGGL(k_adam, dim3((unsigned)bx, (unsigned)n), dim3(256), 0, st, a);
+        hipLaunchKernelGGL(k_adam, dim3((unsigned)bx, (unsigned)p.n), dim3(256), 0, st, a);
     return hipGetLastError();
 }
 

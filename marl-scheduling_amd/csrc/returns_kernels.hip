@@ -7,6 +7,7 @@
 
 #include "../../include/marlsched.h"
 #include "ms_common.h"
+#include "ms_returns.h"
 
 namespace ms {
 
@@ -151,19 +152,18 @@ __global__ void __launch_bounds__(256, 2) k_unit_returns_reg(const void* __restr
     }
 }
 
-hipError_t launch_unit_returns(const void* rewards, int is_i32, int T, int64_t E, int U, const int32_t* unit_of_group,
-                               int G, double gamma, float* out, hipStream_t st) {
-    const int64_t M = E * G;
+hipError_t launch_unit_returns(const UnitReturns& a, hipStream_t st) {
+    const int64_t M = a.E * a.G;
     if (M <= 0) return hipSuccess;
-    if (T == kRetRegT) {
-        auto kreg = is_i32 ? k_unit_returns_reg<true> : k_unit_returns_reg<false>;
-        hipLaunchKernelGGL(kreg, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, st, rewards, E, U, unit_of_group, G,
-                           gamma, out);
+    if (a.T == kRetRegT) {
+        auto kreg = a.is_i32 ? k_unit_returns_reg<true> : k_unit_returns_reg<false>;
+        hipLaunchKernelGGL(kreg, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, st, a.rewards, a.E, a.U,
+                           a.unit_of_group, a.G, a.gamma, a.out);
         return hipGetLastError();
     }
-    auto kern = is_i32 ? k_unit_returns<true> : k_unit_returns<false>;
-    hipLaunchKernelGGL(kern, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, st, rewards, T, E, U, unit_of_group, G,
-                       gamma, out);
+    auto kern = a.is_i32 ? k_unit_returns<true> : k_unit_returns<false>;
+    hipLaunchKernelGGL(kern, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, st, a.rewards, a.T, a.E, a.U,
+                       a.unit_of_group, a.G, a.gamma, a.out);
     return hipGetLastError();
 }
 
