@@ -603,6 +603,33 @@ int ms_env_rollout_act_free(ms_env* env, const ms_actions* act, const ms_obs_out
                             const ms_event_out* ev, const ms_fused_act_free* next, const ms_round_strides_free* strides,
                             int32_t n_rounds, int32_t act_after_last, void* stream);
 
+/* Compact offer observations (detect with dlsym; MS_ABI_VERSION is unchanged). The N*L offer rows a round writes for
+ * a replica differ only in the slot's (prio, rem) pair at bytes 2C, 2C + 1: row (e, u) = tmpl[e] with pair[e][u] (low
+ * byte first) at byte 2C, where tmpl[e] [off_obs_stride] holds the cores' (prio, rem) pairs and zeros after them. */
+typedef struct ms_offer_compact {
+    int8_t* tmpl;      /* [E][off_obs_stride] the first round's templates */
+    uint16_t* pair;    /* [E][N*L] the first round's slot pairs */
+    int64_t tmpl_stride, pair_stride; /* bytes between two rounds' arrays */
+} ms_offer_compact;
+
+/* ms_env_rollout_act_free with compact offer observations: every round writes its templates and pairs (advanced by t
+ * strides of `compact`), and only round n_rounds - 1 also writes its offer rows, to obs->offer advanced by
+ * n_rounds - 1 strides as ms_env_rollout_act_free does; the offer rows of the earlier rounds' slots are left
+ * untouched (ms_offer_expand makes them). Everything else, the acting included, is ms_env_rollout_act_free's, bit for
+ * bit. Both arrays and both strides 4-byte aligned (pair and its stride 2-byte when N*L is odd). */
+int ms_env_rollout_act_free_compact(ms_env* env, const ms_actions* act, const ms_obs_out* obs,
+                                    const ms_reward_out* rew, const ms_event_out* ev, const ms_fused_act_free* next,
+                                    const ms_round_strides_free* strides, const ms_offer_compact* compact,
+                                    int32_t n_rounds, int32_t act_after_last, void* stream);
+
+/* n records of offer rows [n][n_units][stride] (in_dim = 2C + 2 used bytes, the slot pair last) into their compact
+ * form, tmpl [n][stride] (record m's row 0 without its pair) and pair [n][n_units], and back (every byte of the rows
+ * is written). rows and tmpl 4-byte aligned. */
+int ms_offer_compress(const int8_t* rows, int64_t n, int32_t n_units, int32_t stride, int32_t in_dim, int8_t* tmpl,
+                      uint16_t* pair, void* stream);
+int ms_offer_expand(const int8_t* tmpl, const uint16_t* pair, int64_t n, int32_t n_units, int32_t stride,
+                    int32_t in_dim, int8_t* rows, void* stream);
+
 /* The acceptor outputs of ms_env_rollout_act_free(..., next->defer_common = 1, ...) that the launch left: every
  * acting round's items (e, a, c) with core_owner[e][c] != a + 1, with the same obs, next and strides as that call
  * and next->offset_dev holding the value it held then (the Philox offsets of those rounds). On any stream ordered
@@ -700,6 +727,13 @@ typedef struct ms_ppo_grads {  /* device outputs, [G][...] like the weights */
 size_t ms_ppo_workspace_bytes(const ms_mlp_params* actor, int64_t rows);
 int ms_ppo_grad(const ms_mlp_params* actor, const ms_mlp_params* critic, const ms_ppo_batch* batch, float eps_clip,
                 void* workspace, size_t workspace_bytes, const ms_ppo_grads* grads, void* stream);
+/* ms_ppo_grad on compact offer rows (ms_offer_compact): tmpl [R][stride] and pair [R][U] stand for
+ * batch->states [R][U][stride], which is not read (may be NULL); gradients and loss terms are bit-identical to
+ * ms_ppo_grad on the expanded rows. For core choosers: an even in_dim in (4, 64), <= 16 actions, no common_row,
+ * core_owner or unit_stride; MS_EINVAL otherwise. */
+int ms_ppo_grad_offer_compact(const ms_mlp_params* actor, const ms_mlp_params* critic, const ms_ppo_batch* batch,
+                              const int8_t* tmpl, const uint16_t* pair, float eps_clip, void* workspace,
+                              size_t workspace_bytes, const ms_ppo_grads* grads, void* stream);
 
 /* ---- aggregated agents (AggregatedAgent Agent.py:73-140, AggregatedFixPricePPOAgent :359-391,
  * FullyAggregatedFixPricePPOAgent :393-492) around ms_env_step ----

@@ -139,6 +139,21 @@ def _load():
                                     ct.POINTER(abi.MsWideBatch), ct.c_float, P, ct.c_size_t,
                                     ct.POINTER(abi.MsPpoGrads), P]),
     }
+    # entry points added without an ABI step (compact offer observations): a library of this ABI built before them
+    # loads without them, and their users ask has()
+    optional = {
+        "ms_env_rollout_act_free_compact": (ct.c_int, [P, ct.POINTER(abi.MsActions), ct.POINTER(abi.MsObsOut),
+                                                       ct.POINTER(abi.MsRewardOut), ct.POINTER(abi.MsEventOut),
+                                                       ct.POINTER(abi.MsFusedActFree),
+                                                       ct.POINTER(abi.MsRoundStridesFree),
+                                                       ct.POINTER(abi.MsOfferCompact), i32, i32, P]),
+        "ms_offer_compress": (ct.c_int, [P, i64, i32, i32, i32, P, P, P]),
+        "ms_offer_expand": (ct.c_int, [P, P, i64, i32, i32, i32, P, P]),
+        "ms_ppo_grad_offer_compact": (ct.c_int, [ct.POINTER(abi.MsMlpParams), ct.POINTER(abi.MsMlpParams),
+                                                 ct.POINTER(abi.MsPpoBatch), P, P, ct.c_float, P, ct.c_size_t,
+                                                 ct.POINTER(abi.MsPpoGrads), P]),
+    }
+    sig.update({name: v for name, v in optional.items() if hasattr(L, name)})
     L.ms_abi_version.restype = ct.c_int
     version = L.ms_abi_version()
     # ABI 14 added ms_bdqn_update*, 15 ms_bdqn_act_compact, 16 ms_mlp_params.row_base (a trailing field an
@@ -198,6 +213,7 @@ EXPORTED = (
     "ms_regen_agent_rows", "ms_bdqn_workspace_bytes", "ms_bdqn_prepare", "ms_bdqn_layer1_scratch_bytes", "ms_bdqn_layer1_compact",
     "ms_bdqn_act", "ms_bdqn_act_compact", "ms_bdqn_update_workspace_bytes", "ms_bdqn_update", "ms_wide_act", "ms_wide_workspace_bytes",
     "ms_wide_grad",
+    "ms_env_rollout_act_free_compact", "ms_offer_compress", "ms_offer_expand", "ms_ppo_grad_offer_compact",
 )
 
 

@@ -236,6 +236,10 @@ class MsRoundStridesFree(ct.Structure):  # ms_round_strides_free (ABI 18): bytes
         ("next_own_action", ct.c_int64), ("next_own_logprob", ct.c_int64)]
 
 
+class MsOfferCompact(ct.Structure):  # ms_offer_compact: the first round's templates and pairs, bytes per round
+    _fields_ = [("tmpl", ct.c_void_p), ("pair", ct.c_void_p), ("tmpl_stride", ct.c_int64), ("pair_stride", ct.c_int64)]
+
+
 class MsQnetParams(ct.Structure):
     _fields_ = [("w1", ct.c_void_p), ("b1", ct.c_void_p), ("w2", ct.c_void_p), ("b2", ct.c_void_p),
                 ("in_dim", ct.c_int32), ("hidden", ct.c_int32), ("n_actions", ct.c_int32), ("n_groups", ct.c_int32)]

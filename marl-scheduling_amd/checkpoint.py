@@ -288,9 +288,11 @@ def load(tr, path: str) -> dict:
         tr.episode_log = _decode(state["episode_log"])
     tr._policy_version += 1   # the acting tables are rebuilt from the loaded policy_old
     tr._rings_pending = False  # the rings belong to no rollout of this state
-    # ring slot 0: the observation the next rollout acts on, as __init__ emits it
+    tr._offers_pending = False
+    # ring slot 0: the observation the next rollout acts on, as __init__ emits it (offer rows; a compact rollout
+    # compresses them itself)
     for env, e0, e1 in tr.env.parts:
-        env.reset(dict(tr._acc_out(0, e0, e1), offer=tr.off_obs[0][e0:e1]))
+        env.reset(dict(tr._acc_out(0, e0, e1), offer=tr._off_obs[0][e0:e1]))
     torch.cuda.synchronize(dev)
     return manifest
 

@@ -183,4 +183,57 @@ hipError_t launch_regen_agent_rows(const RegenArgs& g, hipStream_t s) {
     hipLaunchKernelGGL(k_regen_agent_rows, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, g);
     return hipGetLastError();
 }
+
+// The compact form of a rollout's offer rows (OffCompact, ms_layout.h): the U rows of a record share every byte but
+// the slot pair at bytes col, col + 1 (col = 2C, even). One thread per dword of the compact record: stride / 4 of
+// the template (row 0 with the pair bytes cleared), then its pairs two by two.
+__global__ void __launch_bounds__(256) k_offer_compress(OffRowsArgs g) {
+    const int nw = g.stride >> 2, np = (g.U + 1) >> 1, per = nw + np;
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    const long long m = i / per;
+    if (m >= g.n) return;
+    const int w = (int)(i - m * per);
+    const int8_t* rows = g.rows + (size_t)m * g.U * g.stride;
+    if (w < nw) {
+        uint32_t v = *reinterpret_cast<const uint32_t*>(rows + 4 * w);
+        if (w == g.col >> 2) v &= ~(0xffffu << (8 * (g.col & 3)));
+        *reinterpret_cast<uint32_t*>(g.tmpl + (size_t)m * g.stride + 4 * w) = v;
+    } else {
+        for (int u = 2 * (w - nw); u < min(2 * (w - nw) + 2, g.U); u++) {
+            const uint8_t* r = reinterpret_cast<const uint8_t*>(rows) + (size_t)u * g.stride + g.col;
+            g.pair[(size_t)m * g.U + u] = (uint16_t)(r[0] | r[1] << 8);
+        }
+    }
+}
+// ... and back: one thread per dword of the rows
+__global__ void __launch_bounds__(256) k_offer_expand(OffRowsArgs g) {
+    const int nw = g.stride >> 2;
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    const long long row = i / nw;
+    if (row >= g.n * g.U) return;
+    const int w = (int)(i - row * nw);
+    const long long m = row / g.U;
+    uint32_t v = *reinterpret_cast<const uint32_t*>(g.tmpl + (size_t)m * g.stride + 4 * w);
+    if (w == g.col >> 2) v |= (uint32_t)g.pair[row] << (8 * (g.col & 3));
+    *reinterpret_cast<uint32_t*>(g.rows + (size_t)row * g.stride + 4 * w) = v;
+}
+
+static bool off_rows_ok(const OffRowsArgs& g) {
+    return g.rows && g.tmpl && g.pair && g.n >= 0 && g.U >= 1 && g.stride >= 4 && (g.stride & 3) == 0 && g.col >= 0 &&
+           (g.col & 1) == 0 && g.col + 2 <= g.stride;
+}
+hipError_t launch_offer_compress(const OffRowsArgs& g, hipStream_t s) {
+    if (!off_rows_ok(g)) return hipErrorInvalidValue;
+    const long long n = g.n * ((g.stride >> 2) + ((g.U + 1) >> 1));
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_offer_compress, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, g);
+    return hipGetLastError();
+}
+hipError_t launch_offer_expand(const OffRowsArgs& g, hipStream_t s) {
+    if (!off_rows_ok(g)) return hipErrorInvalidValue;
+    const long long n = g.n * g.U * (g.stride >> 2);
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_offer_expand, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, g);
+    return hipGetLastError();
+}
 }  // namespace ms

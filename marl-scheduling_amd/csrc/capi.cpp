@@ -423,9 +423,10 @@ int ms_env_rollout_act_free_supported(const ms_env* env) {
     return env && env->cfg.free_prices && ms::env_rollout_free_supported(env->P) ? 1 : 0;
 }
 
-int ms_env_rollout_act_free(ms_env* env, const ms_actions* act, const ms_obs_out* obs, const ms_reward_out* rew,
+// ms_env_rollout_act_free (oc NULL) and ms_env_rollout_act_free_compact
+static int rollout_act_free(ms_env* env, const ms_actions* act, const ms_obs_out* obs, const ms_reward_out* rew,
                             const ms_event_out* ev, const ms_fused_act_free* next, const ms_round_strides_free* strides,
-                            int32_t n_rounds, int32_t act_after_last, void* stream) {
+                            const ms_offer_compact* oc, int32_t n_rounds, int32_t act_after_last, void* stream) {
     if (!env || !act || !next || !strides) return fail(MS_EINVAL, "env/act/next/strides is NULL");
     const ms::Params& P = env->P;
     auto bad = [&](const char* why) { return fail(MS_EINVAL, "ms_env_rollout_act_free: %s", why); };
@@ -468,10 +469,65 @@ int ms_env_rollout_act_free(ms_env* env, const ms_actions* act, const ms_obs_out
     if (rc != MS_OK) return rc;
     const ms::FusedActFree fa = free_act_args(*next);
     const ms::RoundStrideFree st = free_strides(*strides);
-    HIP_TRY(ms::launch_env_rollout_act_free(*env, io, fa, st, n_rounds, act_after_last ? 1 : 0, (hipStream_t)stream));
+    ms::OffCompact c_off{};
+    if (oc) {
+        // (an even N*L: a replica's pairs are copied as dwords)
+        const int pa = (N * L) & 1 ? 1 : 3;
+        if (!oc->tmpl || !oc->pair || ((uintptr_t)oc->tmpl & 3) || ((uintptr_t)oc->pair & pa) ||
+            (oc->tmpl_stride & 3) || (oc->pair_stride & pa))
+            return bad("compact offer observations: tmpl and pair given, tmpl and its stride 4-byte aligned, pair "
+                       "and its stride 4-byte (an odd N*L: 2-byte) aligned");
+        c_off = ms::OffCompact{oc->tmpl, oc->pair, oc->tmpl_stride, oc->pair_stride};
+    }
+    HIP_TRY(ms::launch_env_rollout_act_free(*env, io, fa, st, c_off, n_rounds, act_after_last ? 1 : 0,
+                                            (hipStream_t)stream));
     if (!next->defer_common)
         HIP_TRY(ms::launch_env_fill_common(P, env->E, io, fa, st, n_rounds, act_after_last ? 1 : 0, (hipStream_t)stream));
     env->round += n_rounds;
+    return MS_OK;
+}
+
+int ms_env_rollout_act_free(ms_env* env, const ms_actions* act, const ms_obs_out* obs, const ms_reward_out* rew,
+                            const ms_event_out* ev, const ms_fused_act_free* next, const ms_round_strides_free* strides,
+                            int32_t n_rounds, int32_t act_after_last, void* stream) {
+    return rollout_act_free(env, act, obs, rew, ev, next, strides, nullptr, n_rounds, act_after_last, stream);
+}
+
+int ms_env_rollout_act_free_compact(ms_env* env, const ms_actions* act, const ms_obs_out* obs,
+                                    const ms_reward_out* rew, const ms_event_out* ev, const ms_fused_act_free* next,
+                                    const ms_round_strides_free* strides, const ms_offer_compact* compact,
+                                    int32_t n_rounds, int32_t act_after_last, void* stream) {
+    if (!compact) return fail(MS_EINVAL, "ms_env_rollout_act_free_compact: compact is NULL");
+    return rollout_act_free(env, act, obs, rew, ev, next, strides, compact, n_rounds, act_after_last, stream);
+}
+
+static int offer_rows_args(const char* who, int8_t* rows, int64_t n, int32_t n_units, int32_t stride, int32_t in_dim,
+                           int8_t* tmpl, uint16_t* pair, ms::OffRowsArgs* g) {
+    if (!rows || !tmpl || !pair) return fail(MS_EINVAL, "%s: NULL argument", who);
+    if (n < 0 || n_units < 1 || in_dim < 2 || (in_dim & 1) || stride < in_dim || (stride & 3))
+        return fail(MS_EINVAL, "%s: needs n >= 0, n_units >= 1, an even in_dim >= 2 and a stride >= in_dim in whole dwords",
+                    who);
+    if (((uintptr_t)rows & 3) || ((uintptr_t)tmpl & 3) || ((uintptr_t)pair & 1))
+        return fail(MS_EINVAL, "%s: misaligned array", who);
+    if (n * n_units * (stride / 4) / 256 >= (1LL << 31)) return fail(MS_EINVAL, "%s: too many rows for one launch", who);
+    *g = ms::OffRowsArgs{rows, tmpl, pair, n, n_units, stride, in_dim - 2};
+    return MS_OK;
+}
+int ms_offer_compress(const int8_t* rows, int64_t n, int32_t n_units, int32_t stride, int32_t in_dim, int8_t* tmpl,
+                      uint16_t* pair, void* stream) {
+    ms::OffRowsArgs g;
+    int rc = offer_rows_args("ms_offer_compress", const_cast<int8_t*>(rows), n, n_units, stride, in_dim, tmpl, pair, &g);
+    if (rc) return rc;
+    HIP_TRY(ms::launch_offer_compress(g, (hipStream_t)stream));
+    return MS_OK;
+}
+int ms_offer_expand(const int8_t* tmpl, const uint16_t* pair, int64_t n, int32_t n_units, int32_t stride,
+                    int32_t in_dim, int8_t* rows, void* stream) {
+    ms::OffRowsArgs g;
+    int rc = offer_rows_args("ms_offer_expand", rows, n, n_units, stride, in_dim, const_cast<int8_t*>(tmpl),
+                             const_cast<uint16_t*>(pair), &g);
+    if (rc) return rc;
+    HIP_TRY(ms::launch_offer_expand(g, (hipStream_t)stream));
     return MS_OK;
 }
 
@@ -1061,8 +1117,10 @@ size_t ms_ppo_workspace_bytes(const ms_mlp_params* a, int64_t rows) {
     return b;
 }
 
-int ms_ppo_grad(const ms_mlp_params* a, const ms_mlp_params* c, const ms_ppo_batch* b, float eps_clip, void* ws,
-                size_t ws_bytes, const ms_ppo_grads* g, void* stream) {
+// ms_ppo_grad (tmpl / pair NULL) and ms_ppo_grad_offer_compact
+static int ppo_grad(const ms_mlp_params* a, const ms_mlp_params* c, const ms_ppo_batch* b, const int8_t* tmpl,
+                    const uint16_t* pair, float eps_clip, void* ws, size_t ws_bytes, const ms_ppo_grads* g,
+                    void* stream) {
     if (!a || !c || !b || !g || !ws) return fail(MS_EINVAL, "NULL argument");
     if (a->hidden != 16 || c->hidden != 16) return fail(MS_EINVAL, "hidden width must be 16");
     if (c->n_actions != 1 || c->in_dim != a->in_dim || c->n_groups != a->n_groups)
@@ -1071,8 +1129,16 @@ int ms_ppo_grad(const ms_mlp_params* a, const ms_mlp_params* c, const ms_ppo_bat
         return fail(MS_EINVAL, "in_dim must be in [1, 256] and n_actions in [1, 128]");
     if (b->stride < a->in_dim || (b->stride & 3) || b->T < 1 || b->E < 1 || b->U < 1)
         return fail(MS_EINVAL, "bad batch shape");
-    if (!b->states || !b->actions || !b->old_logprobs || !b->returns || !b->unit_of_group)
+    if ((!b->states && !tmpl) || !b->actions || !b->old_logprobs || !b->returns || !b->unit_of_group)
         return fail(MS_EINVAL, "NULL batch pointer");
+    if (tmpl) {
+        if (!pair || ((uintptr_t)tmpl & 3) || ((uintptr_t)pair & 1))
+            return fail(MS_EINVAL, "compact offer rows: tmpl and pair given and aligned");
+        if (b->common_row || b->core_owner || b->unit_stride != 0 || ppo_keyable(a) || (a->in_dim & 1) ||
+            a->in_dim >= 64 || a->n_actions > 16)
+            return fail(MS_EINVAL, "compact offer rows: rows [R][U] of an even in_dim in (4, 64) with <= 16 actions, no "
+                                   "common row, owners or unit-major rings");
+    }
     if (b->core_owner && (!b->common_row || b->n_cores < 1 || b->U % b->n_cores != 0 || b->stride < 16))
         return fail(MS_EINVAL, "compact rows need common_row, stride >= 16 and U = n_agents * n_cores");
     const int64_t R = (int64_t)b->T * b->E;
@@ -1082,7 +1148,8 @@ int ms_ppo_grad(const ms_mlp_params* a, const ms_mlp_params* c, const ms_ppo_bat
     ms::PpoArgs p{};
     p.w1 = a->w1; p.b1 = a->b1; p.w2 = a->w2; p.b2 = a->b2; p.w3 = a->w3; p.b3 = a->b3;
     p.cw1 = c->w1; p.cb1 = c->b1; p.cw2 = c->w2; p.cb2 = c->b2; p.cw3 = c->w3; p.cb3 = c->b3;
-    p.states = b->states;
+    p.states = tmpl ? tmpl : b->states;
+    p.off_pair = tmpl ? pair : nullptr;
     p.actions = b->actions;
     p.old_lp = b->old_logprobs;
     p.rrs = b->unit_stride ? 1 : b->U;
@@ -1184,6 +1251,18 @@ int ms_ppo_grad(const ms_mlp_params* a, const ms_mlp_params* c, const ms_ppo_bat
     ms::GradOut go{g->w1, g->b1, g->w2, g->b2, g->w3, g->b3, g->cw1, g->cb1, g->cw2, g->cb2, g->cw3, g->cb3, g->loss};
     HIP_TRY(ms::launch_ppo_grad(p, go, (hipStream_t)stream));
     return MS_OK;
+}
+
+int ms_ppo_grad(const ms_mlp_params* a, const ms_mlp_params* c, const ms_ppo_batch* b, float eps_clip, void* ws,
+                size_t ws_bytes, const ms_ppo_grads* g, void* stream) {
+    return ppo_grad(a, c, b, nullptr, nullptr, eps_clip, ws, ws_bytes, g, stream);
+}
+
+int ms_ppo_grad_offer_compact(const ms_mlp_params* a, const ms_mlp_params* c, const ms_ppo_batch* b,
+                              const int8_t* tmpl, const uint16_t* pair, float eps_clip, void* ws, size_t ws_bytes,
+                              const ms_ppo_grads* g, void* stream) {
+    if (!tmpl || !pair) return fail(MS_EINVAL, "ms_ppo_grad_offer_compact: tmpl / pair is NULL");
+    return ppo_grad(a, c, b, tmpl, pair, eps_clip, ws, ws_bytes, g, stream);
 }
 
 int ms_aggregate_obs(const ms_config* cfg, int64_t E, const int8_t* acc_obs, const int8_t* off_obs,

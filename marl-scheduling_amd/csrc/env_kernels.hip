@@ -742,6 +742,7 @@ struct RolloutFreeArgs {
     int prio;      // bit 0: the workgroup's waves 4.. at raised issue priority while acting, bit 1: during the env
                    // round, bit 2: the acting's waves paced against their SIMD partners (act_free pace_on)
     int separate;  // (STAG kernels) != 0: the env rounds at priority 3, the acting by stagger_upper_pair
+    OffCompact oc;  // tmpl set: the rounds' offer observations compact, the rows by the last round alone
 };
 // The CU a wave runs on, 12 bits: HW_REG_XCC_ID's XCC above HW_REG_HW_ID's SE, SH and CU fields (bits 15..8).
 constexpr int kCuKeys = 1 << 12;
@@ -848,6 +849,11 @@ __global__ void __launch_bounds__(512, 4) k_env_rollout_act_free(RolloutFreeArgs
         io.rew_acc = advance(io.rew_acc, t * st.rew_acc);
         io.rew_agent = advance(io.rew_agent, t * st.rew_agent);
         io.rew_auct = advance(io.rew_auct, t * st.rew_auct);
+        // compact offer observations: the template and the pairs every round; the acting below reads the LDS
+        // sources either way, and the rows are for whoever reads the launch's last observation
+        int8_t* const oc_tmpl = advance(A.oc.tmpl, t * A.oc.tmpl_stride);
+        uint16_t* const oc_pair = advance(A.oc.pair, t * A.oc.pair_stride);
+        if (oc_tmpl && t + 1 < n_rounds) io.obs_off = nullptr;
         FREE_MARK(-1);
         // (the younger half of the workgroup's waves otherwise trails the older at every barrier: issue goes by
         //  priority, then age)
@@ -864,8 +870,9 @@ __global__ void __launch_bounds__(512, 4) k_env_rollout_act_free(RolloutFreeArgs
         const int8_t* acc_lds = t > 0 && A.fa.own_action
                                     ? reinterpret_cast<const int8_t*>(smem_free + fl.accx) + wave * kFreeEPW * g.N * g.C
                                     : nullptr;
-        env_round<kWave / kFreeEPW, false, true, SH, MET, MET>(A.P, A.E, A.recs, A.mt, A.liab, io, wslot, lane,
-                                                               smem_free + wave * free_slot(g), acc_lds);
+        env_round<kWave / kFreeEPW, false, true, SH, MET, MET, false, true>(
+            A.P, A.E, A.recs, A.mt, A.liab, io, wslot, lane, smem_free + wave * free_slot(g), acc_lds, nullptr, oc_tmpl,
+            oc_pair);
         if (up) __builtin_amdgcn_s_setprio(0);
         if constexpr (STAG) {
             if (prio_rank >= 0) {  // this round's acting: the pair by now's clock slice
@@ -1137,11 +1144,13 @@ static hipError_t launch_rollout_free_sh(const RolloutFreeArgs& A, hipStream_t s
     return hipGetLastError();
 }
 hipError_t launch_env_rollout_act_free(const EnvDev& d, const StepIO& io, const FusedActFree& fa,
-                                       const RoundStrideFree& st, int n_rounds, int act_last, hipStream_t s) {
+                                       const RoundStrideFree& st, const OffCompact& oc, int n_rounds, int act_last,
+                                       hipStream_t s) {
     if (!env_rollout_free_supported(d.P) || io.act_acc == nullptr || io.obs_acc != nullptr || io.ev_acc != nullptr ||
-        io.ev_term != nullptr || n_rounds < 1)
+        io.ev_term != nullptr || n_rounds < 1 || (oc.tmpl == nullptr) != (oc.pair == nullptr))
         return hipErrorInvalidValue;
-    const RolloutFreeArgs A{d.P, d.E, d.recs, d.mt, d.liab, io, fa, st, n_rounds, act_last, kFreePrio, kFreeSeparate};
+    const RolloutFreeArgs A{d.P, d.E, d.recs, d.mt, d.liab, io, fa, st, n_rounds, act_last, kFreePrio, kFreeSeparate,
+                            oc};
 #ifndef MS_NO_FIXED_SHAPES
     if (is_shape<8, 8, 3, 1>(d.P)) return launch_rollout_free_sh<FixShape<8, 8, 3, 1>>(A, s);
 #endif

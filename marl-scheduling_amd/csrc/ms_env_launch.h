@@ -62,9 +62,11 @@ hipError_t launch_env_step_act(const EnvDev& d, const StepIO& io, const FusedAct
 // n_rounds of launch_env_step_act in one launch, round t's arrays st's strides past round 0's
 hipError_t launch_env_rollout_act(const EnvDev& d, const StepIO& io, const FusedAct& fa, const RoundStride& st,
                                   int n_rounds, int act_last, uint64_t hc_mask, hipStream_t s);
-// the same for a locally shared free-price env; leaves the acceptor items launch_env_fill_common samples
+// the same for a locally shared free-price env; leaves the acceptor items launch_env_fill_common samples.
+// oc.tmpl set: compact offer observations every round, io.obs_off's rows by the last round alone (OffCompact{}: rows)
 hipError_t launch_env_rollout_act_free(const EnvDev& d, const StepIO& io, const FusedActFree& fa,
-                                       const RoundStrideFree& st, int n_rounds, int act_last, hipStream_t s);
+                                       const RoundStrideFree& st, const OffCompact& oc, int n_rounds, int act_last,
+                                       hipStream_t s);
 // random.randrange(n) of replica e's generator into *out (device word)
 hipError_t launch_env_randbelow(const EnvDev& d, int64_t e, uint32_t n, uint32_t* out, hipStream_t s);
 // the hard-coded auctioneer's actions [E][C] of the current state

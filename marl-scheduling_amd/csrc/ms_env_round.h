@@ -683,12 +683,15 @@ __device__ __forceinline__ void emit_rows(uint32_t* base, int64_t e, int64_t E, 
 }
 
 // All observations of env e (dst == NULL skips a kind; a padding group passes write = false).
+// oc_tmpl / oc_pair (OffCompact, both or neither): the offer rows' sources themselves, the template [E][off_stride]
+// and the slot pairs [E][NL]; the sources are built for them also when off == NULL.
 template <int LPE>
-__device__ void emit_obs(Rec& R, const Geom& P, const M128* mc, const M128* mr, uint8_t* scratch, int8_t* acc,
-                         int8_t* off, int8_t* auct, int8_t* crows, int8_t* cown, int64_t e, int64_t E, bool write,
-                         int gl) {
-    build_obs_sources<LPE>(R, P, mc, mr, scratch, acc != nullptr, auct != nullptr || crows != nullptr, off != nullptr,
-                           gl);
+__device__ __forceinline__ void emit_obs_impl(Rec& R, const Geom& P, const M128* mc, const M128* mr, uint8_t* scratch,
+                                              int8_t* acc, int8_t* off, int8_t* auct, int8_t* crows, int8_t* cown,
+                                              int64_t e, int64_t E, bool write, int gl, int8_t* oc_tmpl,
+                                              uint16_t* oc_pair) {
+    build_obs_sources<LPE>(R, P, mc, mr, scratch, acc != nullptr, auct != nullptr || crows != nullptr,
+                           off != nullptr || oc_tmpl != nullptr, gl);
     if (!write) return;
     const int C = P.C, nw = P.acc_stride / 4, nwo = P.off_stride / 4;
     const uint32_t* crow = reinterpret_cast<const uint32_t*>(scratch);
@@ -720,6 +723,32 @@ __device__ void emit_obs(Rec& R, const Geom& P, const M128* mc, const M128* mr, 
             return v;
         });
     }
+    if (oc_tmpl) {
+        const uint32_t* otmpl = reinterpret_cast<const uint32_t*>(scratch + P.s_otmpl);
+        uint32_t* td = reinterpret_cast<uint32_t*>(oc_tmpl) + e * nwo;
+        for (int k = gl; k < nwo; k += LPE) td[k] = otmpl[k];
+        if ((P.NL & 1) == 0) {  // (both sides dword-aligned: s_slotpair is, and a replica's pairs are NL / 2 dwords)
+            const uint32_t* sp = reinterpret_cast<const uint32_t*>(scratch + P.s_slotpair);
+            uint32_t* pd = reinterpret_cast<uint32_t*>(oc_pair) + e * (P.NL >> 1);
+            for (int k = gl; k < (P.NL >> 1); k += LPE) pd[k] = sp[k];
+        } else {
+            const uint16_t* sp = reinterpret_cast<const uint16_t*>(scratch + P.s_slotpair);
+            for (int s = gl; s < P.NL; s += LPE) oc_pair[e * P.NL + s] = sp[s];
+        }
+    }
+}
+// (two functions, so that the kernels without compact offer observations keep the code they had)
+template <int LPE>
+__device__ void emit_obs(Rec& R, const Geom& P, const M128* mc, const M128* mr, uint8_t* scratch, int8_t* acc,
+                         int8_t* off, int8_t* auct, int8_t* crows, int8_t* cown, int64_t e, int64_t E, bool write,
+                         int gl) {
+    emit_obs_impl<LPE>(R, P, mc, mr, scratch, acc, off, auct, crows, cown, e, E, write, gl, nullptr, nullptr);
+}
+template <int LPE>
+__device__ void emit_obs_compact(Rec& R, const Geom& P, const M128* mc, const M128* mr, uint8_t* scratch, int8_t* acc,
+                                 int8_t* off, int8_t* auct, int8_t* crows, int8_t* cown, int64_t e, int64_t E,
+                                 bool write, int gl, int8_t* oc_tmpl, uint16_t* oc_pair) {
+    emit_obs_impl<LPE>(R, P, mc, mr, scratch, acc, off, auct, crows, cown, e, E, write, gl, oc_tmpl, oc_pair);
 }
 
 // HardcodedAuctioneerAcceptor.selectAction for every core (HardcodedModules.py:54-78,
@@ -940,14 +969,16 @@ constexpr int kLiabPrefetch = 4;  // newest chain entries loaded ahead per core 
 // several in its launch, so quality_sum is added by the leader's ordered read-modify-write (m_load / m_store).
 // HC (the mixed fused kernels, not EXT): the agents of mix->hc_mask play the rules as under EXT, and the rows the
 // round used for them are written back over the supplied ones (io.act_acc / io.act_off: the trainer's ring slot).
-template <int LPE, bool EXT, bool CMP, class SH, bool MET = EXT, bool SEQ = false, bool HC = false>
+template <int LPE, bool EXT, bool CMP, class SH, bool MET = EXT, bool SEQ = false, bool HC = false, bool OC = false>
 __device__ __forceinline__ void env_round(const Params& P, int64_t E, uint8_t* recs, uint32_t* mt, Liab* liab,
                                           const StepIO& io, int64_t slot, int lane_arg = -1,
                                           uint8_t* wave_lds = nullptr, const int8_t* acc_lds = nullptr,
-                                          const MixIO* mix = nullptr) {
+                                          const MixIO* mix = nullptr, int8_t* oc_tmpl = nullptr,
+                                          uint16_t* oc_pair = nullptr) {
     // wave_lds: the wave's part of a multi-wave workgroup's LDS (k_env_rollout_act_free), else the block's;
     // acc_lds: the acceptor actions of the wave's replicas in the LDS ([kWave / LPE][N * C]; read instead of
-    // io.act_acc, which then serves the padding replicas only); mix: k_env_step's mixed population (EXT only)
+    // io.act_acc, which then serves the padding replicas only); mix: k_env_step's mixed population (EXT only);
+    // oc_tmpl / oc_pair (OC): this round's compact offer observations (emit_obs_compact; io.obs_off may then be NULL)
     extern __shared__ __align__(16) uint8_t smem_dyn[];
     uint8_t* const smem_all = wave_lds ? wave_lds : smem_dyn;
     // the shape: a compile-time constant for the BASELINE shapes (offsets fold into immediates,
@@ -1605,8 +1636,13 @@ __device__ __forceinline__ void env_round(const Params& P, int64_t E, uint8_t* r
     MS_MARK(10);
     build_masks<LPE>(R, g, s_mc, s_mr, gl);
     MS_MARK(11);
-    emit_obs<LPE>(R, g, s_mc, s_mr, scratch, CMP ? nullptr : io.obs_acc, io.obs_off, io.obs_auct,
-                  (EXT || CMP) ? io.obs_crow : nullptr, (EXT || CMP) ? io.obs_cown : nullptr, e, E, active, gl);
+    if constexpr (OC)
+        emit_obs_compact<LPE>(R, g, s_mc, s_mr, scratch, CMP ? nullptr : io.obs_acc, io.obs_off, io.obs_auct,
+                              (EXT || CMP) ? io.obs_crow : nullptr, (EXT || CMP) ? io.obs_cown : nullptr, e, E, active,
+                              gl, oc_tmpl, oc_pair);
+    else
+        emit_obs<LPE>(R, g, s_mc, s_mr, scratch, CMP ? nullptr : io.obs_acc, io.obs_off, io.obs_auct,
+                      (EXT || CMP) ? io.obs_crow : nullptr, (EXT || CMP) ? io.obs_cown : nullptr, e, E, active, gl);
     MS_MARK(12);
 #ifdef MS_PHASE_TIMING
     if (lane == 0)

@@ -232,6 +232,26 @@ struct RoundStrideFree {
     int64_t own_action, own_logprob;
 };
 
+// The compact offer observations of k_env_rollout_act_free (ms_env_rollout_act_free_compact): offer row (e, s) of a
+// round is replica e's template, the (prio, rem) pairs of all cores with a zero tail, with slot s's (prio, rem)
+// pair at byte 2C. With tmpl set, every round writes the replica's template and its N*L pairs instead of the N*L
+// rows, and only the launch's last round writes the rows as well (StepIO::obs_off).
+struct OffCompact {
+    int8_t* tmpl;    // [E][off_stride] round 0's, or NULL: every round writes the rows
+    uint16_t* pair;  // [E][N*L]
+    int64_t tmpl_stride, pair_stride;  // bytes between two rounds
+};
+
+// launch arguments of k_offer_compress / k_offer_expand (agg_kernels.hip): n records of U offer rows [stride] with
+// the slot pair at byte col <-> the record's template [stride] and pairs [U] (OffCompact)
+struct OffRowsArgs {
+    int8_t* rows;    // [n][U][stride]
+    int8_t* tmpl;    // [n][stride]
+    uint16_t* pair;  // [n][U]
+    long long n;
+    int U, stride, col;
+};
+
 // The workgroup LDS of k_env_rollout_act_free: the env slices of its kFreeEPW * N replicas (wave w steps
 // replicas kFreeEPW * w ..), then the act area: the price table's key digits (one copy per workgroup) and per
 // wave (= agent) its list of owned-core acceptor rows.

@@ -72,6 +72,9 @@ struct PpoArgs {
     const float* rg_own_lp;    // [R][owner_C]
     uint64_t rg_seed, rg_offset, rg_step;  // ring slot s acted with offset rg_offset + s * rg_step (+ *rg_offset_dev)
     const uint64_t* rg_offset_dev;
+    // compact offer rows (kOffCompact, the plain tile path): states = the rows' templates [R][stride], and row
+    // (r, u) is template r with off_pair[r][u] at bytes D - 2, D - 1 (OffCompact, ms_layout.h); NULL: states [R][U][stride]
+    const uint16_t* off_pair;  // [R][U]
 };
 constexpr int kRegenTabDw = 68;  // Head<2>::table: [32 running sums][32 log-probs][S][last nonzero][2 pad]
 

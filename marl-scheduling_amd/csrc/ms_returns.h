@@ -41,5 +41,8 @@ struct DecodeArgs {
 hipError_t launch_decode_aggregated(const DecodeArgs& a, hipStream_t st);
 // a replay memory's agent rows from its compact records
 hipError_t launch_regen_agent_rows(const RegenArgs& g, hipStream_t s);
+// offer rows -> their records' templates (from each record's row 0) and slot pairs, and back (every row written whole)
+hipError_t launch_offer_compress(const OffRowsArgs& g, hipStream_t s);
+hipError_t launch_offer_expand(const OffRowsArgs& g, hipStream_t s);
 
 }  // namespace ms

@@ -84,6 +84,10 @@ constexpr int kX1 = 16;  // mode bit: the last action tile has exactly one actio
 // Philox draws and the agent's act-time table and takes the own rows' from the rollout's by-core arrays
 // (PpoArgs rg_*), instead of reading every row's from the [R][U] rings
 constexpr int kRegen = 32;
+// mode bit (kPlain only): compact offer rows (PpoArgs off_pair). A lane's state dwords come from the row's template
+// [R][stride] and the row's slot pair [R][U] is ORed into the dword that holds bytes D - 2, D - 1 when the tile
+// takes them: the dwords the rows [R][U][stride] would have given
+constexpr int kOffCompact = 64;
 // kMaskRow: compact acceptor rows of many groups (the divided acceptors), the common rows already
 // summed by k_own_scan / k_own_common: each wave runs the tiles of the rows its group's own-row mask
 // lists, and one wave per group the common rows' virtual tile. kCommonFwd: the forward of the
@@ -136,6 +140,8 @@ __global__ void __launch_bounds__((64 * GradLds<NQ, NT, MODEX>::WPB), ((NQ * NT 
     // sum over the row's lane groups) instead of 12 f32 MFMAs on a tile of 15 padding actions
     constexpr bool X1 = (MODEX & kX1) != 0;
     constexpr bool RG = L::RG;
+    constexpr bool OC = (MODEX & kOffCompact) != 0;
+    static_assert(!OC || MODE == kPlain, "compact offer rows: the plain tile path");
     static_assert(!RG || (MODE == kOwnerRow && L::S1 == 2 && NT == 2), "the regenerating scan: FragLayout<2, 2> tables");
     constexpr int TP = L::TP, TP2 = L::TP2, XPD = L::XPD, S1 = L::S1, W1B = L::W1B;
     constexpr int NTH = 64 * L::WPB, CPW = 4 / L::WPB;  // threads per block, chunks per wave
@@ -688,15 +694,18 @@ __global__ void __launch_bounds__((64 * GradLds<NQ, NT, MODEX>::WPB), ((NQ * NT 
     uint32_t pre[S1][2];
     int pre_act = 0;
     float pre_olp = 0.f, pre_G = 0.f;
-    const int st_rb = (OWNROWS ? p.owner_C : (int)p.rrs) * p.stride;  // bytes between rows
+    [[maybe_unused]] uint16_t pre_pair = 0;
+    const int st_rb = OC ? p.stride : (OWNROWS ? p.owner_C : (int)p.rrs) * p.stride;  // bytes between rows
     const int ac_rb = (int)p.rrs, lp_rb = 4 * (int)p.rrs, rt_rb = 4 * p.ret_ld;
-    const int8_t* st_base =
-        OWNROWS ? p.states + (size_t)own_c * p.stride : p.states + (size_t)u * (size_t)p.rus * p.stride;
+    const int8_t* st_base = OC        ? p.states
+                            : OWNROWS ? p.states + (size_t)own_c * p.stride
+                                      : p.states + (size_t)u * (size_t)p.rus * p.stride;
     const int8_t* ac_base = p.actions + (size_t)u * (size_t)p.rus;
     const float* lp_base = p.old_lp + (size_t)u * (size_t)p.rus;
     const float* rt_base = p.ret + grp;
     struct RowBufs {
         __amdgpu_buffer_rsrc_t st, ac, lp, rt;
+        __amdgpu_buffer_rsrc_t pr;  // (kOffCompact) the slot pairs
     };
     // rows per descriptor before its byte count passes 2^31 - 1 (32-bit scalar compares in the loop)
     const int lim_st = 0x7fffffff / st_rb, lim_lp = 0x7fffffff / max(lp_rb, rt_rb);
@@ -714,6 +723,7 @@ __global__ void __launch_bounds__((64 * GradLds<NQ, NT, MODEX>::WPB), ((NQ * NT 
         b.ac = mk(ac_base, ac_rb, lim_lp);
         b.lp = mk(lp_base, lp_rb, lim_lp);
         b.rt = mk(rt_base, rt_rb, lim_lp);
+        if constexpr (OC) b.pr = mk(p.off_pair + u, 2 * ac_rb, lim_lp);
         return b;
     };
     int ccol[S1][2];  // this lane's dword columns of a row (clamped: the bytes past the row meet zero weights)
@@ -733,6 +743,16 @@ __global__ void __launch_bounds__((64 * GradLds<NQ, NT, MODEX>::WPB), ((NQ * NT 
         pre_act = (int8_t)__builtin_amdgcn_raw_buffer_load_b8(b.ac, (int)__umul24(rel, ac_rb), 0, 0);
         pre_olp = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(b.lp, (int)__umul24(rel, lp_rb), 0, 0));
         pre_G = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(b.rt, (int)__umul24(rel, rt_rb), 0, 0));
+        if constexpr (OC) pre_pair = __builtin_amdgcn_raw_buffer_load_b16(b.pr, (int)__umul24(rel, 2 * ac_rb), 0, 0);
+    };
+    // (kOffCompact) the prefetched row's dwords with its pair in place (a clamped column repeats the last dword, pair
+    // and all, as it does on whole rows)
+    [[maybe_unused]] const int pair_col = 4 * ((D - 2) >> 2), pair_shift = 8 * ((D - 2) & 3);
+    auto pre_dword = [&](int s, int h) {
+        if constexpr (OC)
+            return pre[s][h] | (ccol[s][h] == pair_col ? (uint32_t)pre_pair << pair_shift : 0u);
+        else
+            return pre[s][h];
     };
 
     if constexpr (MODE == kKeyFwd || MODE == kKeyBack) {
@@ -830,7 +850,7 @@ __global__ void __launch_bounds__((64 * GradLds<NQ, NT, MODEX>::WPB), ((NQ * NT 
             const int half = (tile - tile0) & 1;  // position in the tile pair of the dW1 step
             uint32_t xr[S1][2];
 #pragma unroll
-            for (int s = 0; s < S1; s++) xr[s][0] = pre[s][0], xr[s][1] = pre[s][1];
+            for (int s = 0; s < S1; s++) xr[s][0] = pre_dword(s, 0), xr[s][1] = pre_dword(s, 1);
             const bool valid = tile * 16 + j < R;
             const int act = pre_act;
             const float olp = pre_olp, G = pre_G;
@@ -1869,6 +1889,10 @@ static hipError_t launch_grad_t(const PpoArgs& a0, hipStream_t st) {
         }
     }
     if (a.owner) return hipErrorInvalidValue;  // compact rows need the common-row path
+    if (a.off_pair) {  // compact offer rows: core choosers of up to 16 actions on rows of up to 64 bytes, unkeyed
+        if constexpr (NT == 1 && NQ <= 4 && X == 0) return launch_grad_cm<NQ, NT, kPlain | kOffCompact>(a, nb, st);
+        return hipErrorInvalidValue;
+    }
     return launch_grad_cm<NQ, NT, kPlain | X>(a, nb, st);
 }
 

@@ -325,13 +325,17 @@ class BatchedEnv:
                                      stream_ptr(stream)))
 
     def rollout_act_free(self, acceptor, offer_core, obs, rewards, next_act, next_out, strides, n_rounds,
-                         act_after_last=False, events=None, stream=None):
+                         act_after_last=False, events=None, stream=None, compact=None):
         """A locally shared free-price rollout of n_rounds rounds in one launch (ms_env_rollout_act_free; BASELINE
         cfg3): round t steps the replicas with the actions advanced by t strides and next_out["env_price"] as the
         offer prices, writes obs / rewards advanced by t strides, then samples round t + 1's actions into next_act's
         outputs (an abi.MsFusedActFree; next_out: its tensors, round 0's slots) advanced by t strides. Bit-identical
         to n_rounds pairs of step + act_round_free (SchedulingEnvironment.py:150-172, trainPPO.py:160-167).
-        events: as for rollout_act (launch_span, metrics)."""
+        events: as for rollout_act (launch_span, metrics).
+        compact (ms_env_rollout_act_free_compact): (tmpl, pair, tmpl_stride, pair_stride), round 0's templates
+        [E, off_obs_stride] int8 and slot pairs [E, N*L] int16 and the bytes between two rounds' arrays: every round
+        writes those, and only the last round also writes its offer rows (obs["offer"] advanced as without compact;
+        the earlier rounds' slots of that ring are left as they were)."""
         i8, f32 = torch.int8, torch.float32
         assert self.free_prices and next_out["env_price"].numel() == self.E * self.N * self.L
         rings = self._ring_list(acceptor, offer_core, obs, rewards, strides, price=True)
@@ -352,6 +356,16 @@ class BatchedEnv:
                                   (next_out["own_logprob"], strides.next_own_logprob, f32)], n_act)
         assert bool(next_act.own_action) == (next_out.get("own_action") is not None)
         a, o, r, ev = self._step_structs(acceptor, offer_core, next_out["env_price"], None, obs, rewards, events)
+        if compact is not None:
+            tmpl, pair, ts, ps = compact
+            assert tmpl.numel() == self.E * self.shape.off_obs_stride and pair.numel() == self.E * self.N * self.L
+            self.check_rings([(tmpl, ts, i8), (pair, ps, torch.int16)], n_rounds)
+            oc = abi.MsOfferCompact(ptr(tmpl), ptr(pair), int(ts), int(ps))
+            check(lib.ms_env_rollout_act_free_compact(self._h, ct.byref(a), ct.byref(o), ct.byref(r),
+                                                      ct.byref(ev) if ev else None, ct.byref(next_act),
+                                                      ct.byref(strides), ct.byref(oc), int(n_rounds),
+                                                      int(bool(act_after_last)), stream_ptr(stream)))
+            return
         check(lib.ms_env_rollout_act_free(self._h, ct.byref(a), ct.byref(o), ct.byref(r),
                                           ct.byref(ev) if ev else None, ct.byref(next_act), ct.byref(strides),
                                           int(n_rounds), int(bool(act_after_last)), stream_ptr(stream)))

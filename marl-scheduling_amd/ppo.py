@@ -306,6 +306,27 @@ def act_round_free(core: GroupedActorCritic, price: GroupedActorCritic, off_obs,
 
 
 @torch.no_grad()
+def offer_compress(rows, in_dim: int, tmpl, pair, stream=None):
+    """Offer rows [..., U, stride] int8 (in_dim = 2C + 2 used bytes, the slot's pair last) into their compact form
+    (ms_offer_compress): tmpl [..., stride] int8, each record's row 0 without its pair, and pair [..., U] int16."""
+    U, stride = rows.shape[-2:]
+    n = rows.numel() // (U * stride)
+    assert rows.is_contiguous() and tmpl.is_contiguous() and pair.is_contiguous()
+    assert rows.dtype == tmpl.dtype == torch.int8 and pair.dtype == torch.int16
+    assert tmpl.numel() == n * stride and pair.numel() == n * U
+    check(lib.ms_offer_compress(ptr(rows), n, U, stride, int(in_dim), ptr(tmpl), ptr(pair), stream_ptr(stream)))
+
+
+def offer_expand(tmpl, pair, in_dim: int, rows, stream=None):
+    """The inverse of offer_compress (ms_offer_expand): every byte of rows [..., U, stride] is written."""
+    U, stride = rows.shape[-2:]
+    n = rows.numel() // (U * stride)
+    assert rows.is_contiguous() and tmpl.is_contiguous() and pair.is_contiguous()
+    assert rows.dtype == tmpl.dtype == torch.int8 and pair.dtype == torch.int16
+    assert tmpl.numel() == n * stride and pair.numel() == n * U
+    check(lib.ms_offer_expand(ptr(tmpl), ptr(pair), n, U, stride, int(in_dim), ptr(rows), stream_ptr(stream)))
+
+
 def act_round_greedy(core: GroupedActorCritic, price: GroupedActorCritic | None, off_obs, acc: GroupedActorCritic,
                      core_rows, core_owner, common_row, n_cores: int, out: dict, acc_action, stream=None):
     """One round's getActionForAllAgents (SchedulingEnvironment.py:150-172) with every pick greedy
@@ -661,7 +682,7 @@ class PPOGroup:
 
     def fused_epoch(self, states_i8, actions_i8, old_logprobs, returns_teg, unit_of_group, T: int, E: int,
                     stream=None, common_row=None, returns_ld: int = 0, core_owner=None, unit_major: bool = False,
-                    regen: dict | None = None):
+                    regen: dict | None = None, off_compact=None):
         """The gradient half of one K-epoch step of ``update_fused``, for callers that all-reduce
         several groups' gradients in one call (Trainer.update): returns a function that writes this
         epoch's gradient into ``policy``'s .grad tensors (ms_ppo_grad) and returns the per-group loss
@@ -669,8 +690,16 @@ class PPOGroup:
         regen (with core_owner; ms_ppo_batch's ABI 20 fields): dict(frag=the acceptor's ActFrag buffer as it was
         at acting time, own_action / own_logprob [R, C], seed, offset (ring slot 0's acting offset), offset_dev,
         offset_step, row_base, slot0): from ring slot slot0 on the kernel regenerates the common rows' actions and
-        old log-probs and reads the own rows' by core, instead of reading actions_i8 / old_logprobs."""
+        old log-probs and reads the own rows' by core, instead of reading actions_i8 / old_logprobs.
+        off_compact (ms_ppo_grad_offer_compact; states_i8 None): (tmpl [R, stride] int8, pair [R, U] int16), the
+        compact form of offer rows [R, U, stride] (offer_compress): the same gradient bit for bit."""
         pol = self.policy
+        if off_compact is not None:
+            tmpl, pair = off_compact
+            assert states_i8 is None and core_owner is None and common_row is None and not unit_major
+            assert tmpl.dtype == torch.int8 and pair.dtype == torch.int16 and tmpl.is_contiguous() and pair.is_contiguous()
+            assert tmpl.shape[0] == pair.shape[0] and pair.shape == actions_i8.shape
+            states_i8 = tmpl.unsqueeze(1).expand(-1, pair.shape[1], -1)  # (shape only: the kernel reads tmpl / pair)
         # compact acceptor rows (core_owner [R, C]): states are the core rows [R, C, stride], and U
         # (= N*C units) comes from the actions
         if unit_major:  # [U, R(, stride)]: row (r, u) at u * R + r
@@ -682,7 +711,7 @@ class PPOGroup:
         if core_owner is not None:
             n_cores, U = U, actions_i8.shape[1]
             assert common_row is not None and core_owner.shape == (R, n_cores) and core_owner.is_contiguous()
-        assert R == T * E and states_i8.is_contiguous() and actions_i8.is_contiguous()
+        assert R == T * E and (off_compact is not None or states_i8.is_contiguous()) and actions_i8.is_contiguous()
         for prm in pol.parameters():
             if prm.grad is None:
                 prm.grad = torch.zeros_like(prm)
@@ -691,7 +720,7 @@ class PPOGroup:
         c = pol.critic_mlp_params()
         ws_bytes = lib.ms_ppo_workspace_bytes(ct.byref(a), R)
         ws = torch.empty(((ws_bytes + 3) // 4,), dtype=torch.float32, device=states_i8.device)
-        batch = abi.MsPpoBatch(ptr(states_i8), ptr(actions_i8), ptr(old_logprobs), ptr(returns_teg),
+        batch = abi.MsPpoBatch(ptr(states_i8) if off_compact is None else None, ptr(actions_i8), ptr(old_logprobs), ptr(returns_teg),
                                ptr(unit_of_group), stride, T, U, E, ptr(common_row), int(returns_ld),
                                ptr(core_owner), n_cores, int(getattr(self, "row_keys", 0)), R if unit_major else 0)
         if regen is not None:
@@ -707,7 +736,7 @@ class PPOGroup:
         # the structs above hold raw device pointers: the closure keeps every tensor they point into
         # alive until its last launch (a caller's temporaries would otherwise be freed and reused)
         keep = (states_i8, actions_i8, old_logprobs, returns_teg, unit_of_group, common_row, core_owner, ws, loss_buf,
-                regen)
+                regen, off_compact)
 
         def launch(out=None):
             """The gradient; the loss terms [G][3] into out (a caller's [G][3] float32 tensor, e.g. one epoch's
@@ -718,8 +747,13 @@ class PPOGroup:
                 assert out.shape == loss_buf.shape and out.dtype == torch.float32 and out.is_contiguous()
                 g = abi.MsPpoGrads.from_buffer_copy(grads)
                 g.loss = ptr(out)
-            check(lib.ms_ppo_grad(ct.byref(a), ct.byref(c), ct.byref(batch), ct.c_float(self.eps_clip), ptr(ws),
-                                  ws_bytes, ct.byref(g), stream_ptr(stream)))
+            if off_compact is not None:
+                check(lib.ms_ppo_grad_offer_compact(ct.byref(a), ct.byref(c), ct.byref(batch), ptr(off_compact[0]),
+                                                    ptr(off_compact[1]), ct.c_float(self.eps_clip), ptr(ws), ws_bytes,
+                                                    ct.byref(g), stream_ptr(stream)))
+            else:
+                check(lib.ms_ppo_grad(ct.byref(a), ct.byref(c), ct.byref(batch), ct.c_float(self.eps_clip), ptr(ws),
+                                      ws_bytes, ct.byref(g), stream_ptr(stream)))
             return loss_buf if out is None else out
 
         def run():

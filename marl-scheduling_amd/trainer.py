@@ -30,10 +30,10 @@ import numpy as np
 import torch
 
 from . import abi
-from ._lib import ABI_LOADED, capturing, hip_capture, ptr
+from ._lib import ABI_LOADED, capturing, has, hip_capture, ptr
 from .env import BatchedEnv
 from .ppo import (ActFrag, PPOGroup, PriceTable, act_round_free, act_round_greedy, combine_losses, discounted_returns,
-                  offer_act_free, reference_init_order, reference_nets, unit_returns)
+                  offer_act_free, offer_compress, offer_expand, reference_init_order, reference_nets, unit_returns)
 
 
 @dataclass
@@ -277,7 +277,8 @@ class Trainer:
             self.acc_obs = None
         else:
             self.acc_obs = torch.zeros((T + 1, self.E, N * C, s.acc_obs_stride), dtype=torch.int8, device=dev)
-        self.off_obs = torch.zeros((T + 1, self.E, N * L, s.off_obs_stride), dtype=torch.int8, device=dev)
+        # the offer rows' ring; readers outside the rollout and the fused update take the off_obs property
+        self._off_obs = torch.zeros((T + 1, self.E, N * L, s.off_obs_stride), dtype=torch.int8, device=dev)
         # price chooser inputs [T][E][U][4] (unit-major: stored [U][T][E][4], self.price_obs its view)
         self.price_obs_um = None
         if self.free and self.price_unit_major:
@@ -309,7 +310,7 @@ class Trainer:
         self._policy_version = 0  # bumped by update(); the acting tables record the version they saw
         self.iterations = 0
         for env, e0, e1 in self.env.parts:
-            env.reset(dict(self._acc_out(0, e0, e1), offer=self.off_obs[0][e0:e1]))
+            env.reset(dict(self._acc_out(0, e0, e1), offer=self._off_obs[0][e0:e1]))
         # episode metrics (trainPPO.py:153-226): the env kernel adds every round into per-replica
         # accumulators, slot (round // episodeLength) % slots; finished episodes are read after each
         # rollout (metrics.py) and their slots zeroed before reuse
@@ -369,6 +370,22 @@ class Trainer:
         if self.acc_regen:
             self.acc.complete = self._complete_rings
         self._rings_pending = False
+        # compact offer observations: a round's N * L offer rows are the replica's template with the slot's pair at
+        # byte 2C, so the one-launch rollout writes the template and the pairs (off_tmpl / off_pair, 68 B per replica
+        # and round at cfg3 instead of 480) and the offer gradient reads those. Only ring slots 0 (what reset, the
+        # carry or a checkpoint wrote: compressed at the start of every rollout) and T (the last round writes its
+        # rows as well) hold rows after a rollout; whoever reads off_obs gets slots 1..T-1 expanded by one eager
+        # kernel first (_complete_offers). Under acc_regen's conditions.
+        # MS_OFF_COMPACT=0: every round writes the rows and the gradient reads them (A/B runs, equality tests)
+        self.off_compact = (self.fused_rollout_free and self.fused and rollout_streams == 1 and s.off_obs_dim > 4 and
+                            all(has(n) for n in ("ms_env_rollout_act_free_compact", "ms_offer_compress",
+                                                 "ms_offer_expand", "ms_ppo_grad_offer_compact")) and
+                            os.environ.get("MS_OFF_COMPACT", "1") != "0")
+        self.off_tmpl = self.off_pair = None
+        if self.off_compact:
+            self.off_tmpl = torch.zeros((T + 1, self.E, s.off_obs_stride), dtype=torch.int8, device=dev)
+            self.off_pair = torch.zeros((T + 1, self.E, N * L), dtype=torch.int16, device=dev)
+        self._offers_pending = False
         self._fill_args = []
         self.span_every = 0  # > 0: every span_every-th round's env launches record their span (bench)
         self.spans = None
@@ -384,6 +401,20 @@ class Trainer:
             hp.acceptor_gamma = -((1 - 5) / 5) + 0.15
         return cls(cfg, n_envs or abi.NAMED_ENVS[name], arch=kw.pop("arch", arch), hyper=hp, seed=seed, device=device,
                    **kw)
+
+    @property
+    def off_obs(self):
+        """The offer rows' ring [T + 1, E, N*L, stride], complete (after a compact rollout: slots 1..T-1 expanded)."""
+        self._complete_offers()
+        return self._off_obs
+
+    def _complete_offers(self):
+        """The offer rows of ring slots 1..T-1 a compact rollout left out: one eager expansion of the compact rings
+        at the first read after the rollout, never inside a capture (as _complete_rings)."""
+        if self._offers_pending and not capturing():
+            self._offers_pending = False
+            if self.T > 1:
+                offer_expand(self.off_tmpl[1:self.T], self.off_pair[1:self.T], self.off.D, self._off_obs[1:self.T])
 
     def _acc_out(self, t, e0, e1):
         """The env's acceptor observation outputs for ring slot t, replicas [e0, e1)."""
@@ -428,8 +459,12 @@ class Trainer:
         (trainPPO.py:160-167), part by part: part k's launches go to stream k."""
         if getattr(self, "_acting_version", -1) != self._policy_version:
             self._prepare_acting()
+        self._complete_offers()  # (rows a compact rollout left out are not expanded over this round's later)
         for k in range(len(self.env.parts)):
             self._round_part(t, k)
+        if self.off_compact:  # the round wrote rows: the compact rings the fused update reads follow them
+            for slot in ((0, 1) if t == 0 else (t + 1,)):
+                offer_compress(self._off_obs[slot], self.off.D, self.off_tmpl[slot], self.off_pair[slot])
 
     def _round_part(self, t: int, k: int):
         self._act_part(t, k)
@@ -463,19 +498,19 @@ class Trainer:
                            price_logprob=self.price.logprobs_um[:, t, e0:e1])
                 pus = self.T * self.E
             if self.compact:  # the acceptors too, in the same launch
-                act_round_free(self.off.group.policy_old, self.price.group.policy_old, sl(self.off_obs[t]),
+                act_round_free(self.off.group.policy_old, self.price.group.policy_old, sl(self._off_obs[t]),
                                self.acc.group.policy_old, sl(self.acc_rows[t]), sl(self.acc_owner[t]), self.acc_common,
                                C, seed, base + 1, base + 3, out, sl(self.acc.actions[t]), sl(self.acc.logprobs[t]),
                                offset_dev=self.rng_ctr, stream=st, price_table=self.price_table,
                                price_unit_stride=pus, core_frag=self.off_frag, acc_frag=self.acc_frag,
                                replica_base=rb)
             else:
-                offer_act_free(self.off.group.policy_old, self.price.group.policy_old, sl(self.off_obs[t]), C, seed,
+                offer_act_free(self.off.group.policy_old, self.price.group.policy_old, sl(self._off_obs[t]), C, seed,
                                base + 1, out, offset_dev=self.rng_ctr, stream=st, price_unit_stride=pus,
                                core_frag=self.off_frag, replica_base=rb)
         elif self.compact and ABI_LOADED < 16:
             # (an older A/B library: no fixed-price act_round_free; the two launches)
-            self.off.group.policy_old.act(sl(self.off_obs[t]), N * L, seed, base + 1, action=sl(self.off.actions[t]),
+            self.off.group.policy_old.act(sl(self._off_obs[t]), N * L, seed, base + 1, action=sl(self.off.actions[t]),
                                           logprob=sl(self.off.logprobs[t]), offset_dev=self.rng_ctr, stream=st,
                                           frag=self.off_frag, replica_base=rb)
             self.acc.group.policy_old.act_compact(sl(self.acc_rows[t]), sl(self.acc_owner[t]), N * C, seed, base + 3,
@@ -484,13 +519,13 @@ class Trainer:
                                                   frag=self.acc_frag, replica_base=rb)
         elif self.compact:
             # a fixed-price round: the offer units and the compact acceptors in one launch
-            act_round_free(self.off.group.policy_old, None, sl(self.off_obs[t]), self.acc.group.policy_old,
+            act_round_free(self.off.group.policy_old, None, sl(self._off_obs[t]), self.acc.group.policy_old,
                            sl(self.acc_rows[t]), sl(self.acc_owner[t]), self.acc_common, C, seed, base + 1, base + 3,
                            dict(core_action=sl(self.off.actions[t]), core_logprob=sl(self.off.logprobs[t])),
                            sl(self.acc.actions[t]), sl(self.acc.logprobs[t]), offset_dev=self.rng_ctr, stream=st,
                            core_frag=self.off_frag, acc_frag=self.acc_frag, replica_base=rb)
         else:
-            self.off.group.policy_old.act(sl(self.off_obs[t]), N * L, seed, base + 1, action=sl(self.off.actions[t]),
+            self.off.group.policy_old.act(sl(self._off_obs[t]), N * L, seed, base + 1, action=sl(self.off.actions[t]),
                                           logprob=sl(self.off.logprobs[t]), offset_dev=self.rng_ctr, stream=st,
                                           frag=self.off_frag, replica_base=rb)
         if not self.compact:  # (compact acceptors acted above, in the offers' launch)
@@ -505,7 +540,7 @@ class Trainer:
         st = self.streams[k]
         E, N, C, L = e1 - e0, self.N, self.C, self.L
         sl = lambda x: x[e0:e1]
-        obs = dict(self._acc_out(t + 1, e0, e1), offer=sl(self.off_obs[t + 1]))
+        obs = dict(self._acc_out(t + 1, e0, e1), offer=sl(self._off_obs[t + 1]))
         rew = dict(offer=sl(self.off.rewards[t]).view(E, N, L), acceptor=sl(self.acc.rewards[t]).view(E, N, C),
                    agent=sl(self.agent_reward), auctioneer=sl(self.auct_reward),
                    price=sl(self.price.rewards[t]).view(E, N, L) if self.free else None)
@@ -543,7 +578,7 @@ class Trainer:
         env, e0, e1 = self.env.parts[k]
         E, N, C, L = e1 - e0, self.N, self.C, self.L
         sl = lambda x: x[e0:e1]
-        obs = dict(self._acc_out(1, e0, e1), offer=sl(self.off_obs[1]))
+        obs = dict(self._acc_out(1, e0, e1), offer=sl(self._off_obs[1]))
         rew = dict(offer=sl(self.off.rewards[0]).view(E, N, L), acceptor=sl(self.acc.rewards[0]).view(E, N, C),
                    agent=sl(self.agent_reward), auctioneer=sl(self.auct_reward))
         ev = dict(launch_span=self.spans[0, k]) if self.span_every else None
@@ -551,7 +586,7 @@ class Trainer:
             ev = dict(ev or {}, metrics=self.metric_bufs[k])
         b = lambda x: x.stride(0) * x.element_size()  # bytes between ring slots t and t + 1
         strides = abi.MsRoundStrides(b(self.acc.actions), b(self.off.actions), b(self.acc_rows), b(self.acc_owner),
-                                     b(self.off_obs), b(self.off.rewards), b(self.acc.rewards), 0, 0,
+                                     b(self._off_obs), b(self.off.rewards), b(self.acc.rewards), 0, 0,
                                      b(self.off.actions), b(self.off.logprobs), b(self.acc.actions),
                                      b(self.acc.logprobs), 8)
         env.rollout_act(sl(self.acc.actions[0]).view(E, N, C), sl(self.off.actions[0]).view(E, N, L), obs, rew,
@@ -587,7 +622,7 @@ class Trainer:
         env, e0, e1 = self.env.parts[k]
         E, N, C, L = e1 - e0, self.N, self.C, self.L
         sl = lambda x: x[e0:e1]
-        obs = dict(self._acc_out(1, e0, e1), offer=sl(self.off_obs[1]))
+        obs = dict(self._acc_out(1, e0, e1), offer=sl(self._off_obs[1]))
         rew = dict(offer=sl(self.off.rewards[0]).view(E, N, L), acceptor=sl(self.acc.rewards[0]).view(E, N, C),
                    agent=sl(self.agent_reward), auctioneer=sl(self.auct_reward),
                    price=sl(self.price.rewards[0]).view(E, N, L))
@@ -596,7 +631,7 @@ class Trainer:
             ev = dict(ev or {}, metrics=self.metric_bufs[k])
         b = lambda x: x.stride(0) * x.element_size()  # bytes between ring slots t and t + 1
         strides = abi.MsRoundStridesFree(b(self.acc.actions), b(self.off.actions), b(self.acc_rows), b(self.acc_owner),
-                                         b(self.off_obs), b(self.off.rewards), b(self.price.rewards),
+                                         b(self._off_obs), b(self.off.rewards), b(self.price.rewards),
                                          b(self.acc.rewards), 0, 0, b(self.off.actions), b(self.off.logprobs),
                                          b(self.price_obs), b(self.price.actions), b(self.price.logprobs),
                                          b(self.acc.actions), b(self.acc.logprobs), 8)
@@ -604,8 +639,13 @@ class Trainer:
             strides.next_own_action, strides.next_own_logprob = b(self.acc_own[0]), b(self.acc_own[1])
         nxt, out = self._fused_next_free(1, k)
         nxt.defer_common = int(self.acc_regen)
+        compact = None
+        if self.off_compact:  # (one part) slot 0 from the rows whoever wrote them left, slots 1..T by the launch
+            offer_compress(self._off_obs[0], self.off.D, self.off_tmpl[0], self.off_pair[0], stream=self.streams[k])
+            compact = (self.off_tmpl[1], self.off_pair[1], b(self.off_tmpl), b(self.off_pair))
         env.rollout_act_free(sl(self.acc.actions[0]).view(E, N, C), sl(self.off.actions[0]).view(E, N, L), obs, rew,
-                             nxt, out, strides, self.T, act_after_last=False, events=ev, stream=self.streams[k])
+                             nxt, out, strides, self.T, act_after_last=False, events=ev, stream=self.streams[k],
+                             compact=compact)
         if self.acc_regen:
             # the fill's arguments: the same call with the offsets of this rollout (snapshot). It reads the owners
             # of ring slots >= 1 (_carry_last_observation rewrites slot 0 only) and the acceptor tables of
@@ -703,6 +743,7 @@ class Trainer:
         defer_common (iteration(); acc_regen only): leave the pending acceptor rings to be completed at their
         first read (_complete_rings); otherwise the rings are complete when this returns."""
         self._rings_pending = False  # (rings of an earlier rollout nobody read: overwritten now)
+        self._offers_pending = False
         if not self.use_graph:
             self._rollout_body()
         elif self.graph is None:
@@ -718,6 +759,7 @@ class Trainer:
             self._rings_pending = True
             if not defer_common:
                 self._complete_rings()
+        self._offers_pending = self.off_compact
         self.rounds_done += self.T
 
     # ---- update
@@ -783,6 +825,8 @@ class Trainer:
         if u.unit_major:
             st = self.price_obs_um if u is self.price else None
             return st.reshape(u.U, T * E, u.stride), u.actions_um.reshape(u.U, T * E), u.logprobs_um.reshape(u.U, T * E)
+        if u is self.off and self.off_compact:  # (the fused update: the compact rings stand for the rows)
+            return None, u.actions_raw.view(T * E, u.U), u.logprobs_raw.view(T * E, u.U)
         return (self._states_of(u).reshape(T * E, -1, u.stride), u.actions_raw.view(T * E, u.U),
                 u.logprobs_raw.view(T * E, u.U))
 
@@ -909,10 +953,14 @@ class Trainer:
         owner = self.acc_owner[:T].reshape(T * E, self.C) if (u is self.acc and self.compact) else None
         regen = self._acc_regen_args() if (u is self.acc and self.acc_regen) else None
         rows = self._update_rows(u)
+        compact = None
+        if u is self.off and self.off_compact:
+            compact = (self.off_tmpl[:T].view(T * E, u.stride), self.off_pair[:T].view(T * E, u.U))
         col, seq = 0, []
         for n in counts_u:
             ep = u.group.fused_epoch(*rows, ret_all.view(-1)[col:], sel_u[col:col + n], T, E, common_row=common,
-                                     returns_ld=sel_u.numel(), core_owner=owner, unit_major=u.unit_major, regen=regen)
+                                     returns_ld=sel_u.numel(), core_owner=owner, unit_major=u.unit_major, regen=regen,
+                                     off_compact=compact)
             seq += [ep] * u.group.K
             col += n
         return seq
@@ -972,7 +1020,7 @@ class Trainer:
             self.acc_owner[0].copy_(self.acc_owner[self.T])
         else:
             self.acc_obs[0].copy_(self.acc_obs[self.T])
-        self.off_obs[0].copy_(self.off_obs[self.T])
+        self._off_obs[0].copy_(self._off_obs[self.T])  # (compact: the next rollout compresses slot 0 again)
 
     def iteration(self):
         """One PPO iteration; device time of rollout / update accumulates in self.timings (s)."""
