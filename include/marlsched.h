@@ -19,6 +19,7 @@
  *   ms_policy_act   <- PPO.selectAction / ActorCritic.act  PPOmodules.py:53-63,114-125
  *   ms_policy_act_greedy, ms_act_round_greedy <- the same forward with torch.argmax for the sample
  *                      (evaluating a trained policy; no counterpart in the reference's drivers)
+ *   ms_policy_evaluate <- ActorCritic.evaluate             PPOmodules.py:65-72
  *   ms_discounted_returns, ms_unit_returns <- PPO.update return estimate  PPOmodules.py:128-137
  *
  * Conventions: plain pointers and sizes; every device pointer is a HIP device
@@ -455,6 +456,28 @@ int ms_act_round_free(const ms_mlp_params* core_chooser, const ms_mlp_params* pr
 int ms_policy_act_greedy(const ms_mlp_params* p, const int8_t* obs, int32_t obs_stride, int64_t n_envs,
                          int32_t n_units, int32_t units_per_group, const int8_t* common_row,
                          int8_t* action, float* logprob, void* stream);
+
+/* ActorCritic.evaluate(state, action) (PPOmodules.py:65-72; detect with dlsym: MS_ABI_VERSION is
+ * unchanged): per observation row the log-probability of a
+ * given action, the state value and the policy's entropy. Rows, groups and weight layouts as ms_policy_act:
+ * obs [n_envs][n_units][obs_stride] int8, unit u uses group u / units_per_group, actions [n_envs][n_units] int8.
+ * Each output is [n_envs][n_units] f32 and optional: NULL is neither written nor computed (all three NULL: MS_OK,
+ * nothing launched). critic: the value net's weights in the same layout with n_actions = 1 and the actor's in_dim
+ * and n_groups; it may be NULL when value is NULL. actions may be NULL when logprob is NULL.
+ *   p       = softmax(actor logits) (the normalised probabilities Categorical holds)
+ *   logprob = log(clamp(p[a], eps, 1 - eps)), eps = FLT_EPSILON: what ms_policy_act writes for the action it sampled
+ *   entropy = -sum_k log(clamp(p[k], eps, 1 - eps)) * p[k] over the A actions
+ *   value   = critic(row)
+ * An action byte outside [0, n_actions) reads nothing (the byte is compared, never used as an index) and the row's
+ * logprob is NaN; its value and entropy are unaffected. No RNG is read or advanced; act_frag and row_base are
+ * ignored. MS_EINVAL with a message, nothing launched and no output touched: hidden != 16 (either net), A > 127,
+ * obs_stride > 256 or not a multiple of 4, n_units != units_per_group * n_groups, a critic whose in_dim or n_groups
+ * differs from the actor's or whose n_actions is not 1, logprob without actions, value without critic, obs NULL,
+ * n_envs < 1 or n_envs * n_units * obs_stride >= 2^31. */
+int ms_policy_evaluate(const ms_mlp_params* actor, const ms_mlp_params* critic,
+                       const int8_t* obs, int32_t obs_stride, int64_t n_envs, int32_t n_units,
+                       int32_t units_per_group, const int8_t* actions,
+                       float* logprob, float* value, float* entropy, void* stream);
 
 /* One round's getActionForAllAgents (SchedulingEnvironment.py:150-172), greedy, in one launch (two for shapes
  * without a paired kernel), on the observations ms_env_step emits: offer rows + compact acceptor rows

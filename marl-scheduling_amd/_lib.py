@@ -139,9 +139,12 @@ def _load():
                                     ct.POINTER(abi.MsWideBatch), ct.c_float, P, ct.c_size_t,
                                     ct.POINTER(abi.MsPpoGrads), P]),
     }
-    # entry points added without an ABI step (compact offer observations): a library of this ABI built before them
-    # loads without them, and their users ask has()
+    # entry points added without an ABI step (compact offer observations; ms_policy_evaluate, whose users are
+    # GroupedActorCritic.evaluate_hip and the update diagnostics): a library of this ABI built before them loads
+    # without them, and their users ask has()
     optional = {
+        "ms_policy_evaluate": (ct.c_int, [ct.POINTER(abi.MsMlpParams), ct.POINTER(abi.MsMlpParams), P, i32, i64, i32, i32,
+                                          P, P, P, P, P]),
         "ms_env_rollout_act_free_compact": (ct.c_int, [P, ct.POINTER(abi.MsActions), ct.POINTER(abi.MsObsOut),
                                                        ct.POINTER(abi.MsRewardOut), ct.POINTER(abi.MsEventOut),
                                                        ct.POINTER(abi.MsFusedActFree),
@@ -207,7 +210,7 @@ EXPORTED = (
     "ms_env_rollout_act_free", "ms_env_rollout_act_free_supported", "ms_env_rollout_fill_common", "ms_env_round", "ms_env_flags", "ms_env_randbelow", "ms_env_auctioneer",
     "ms_env_get_rng", "ms_env_set_rng", "ms_env_export",
     "ms_env_import", "ms_env_snapshot", "ms_env_restore", "ms_policy_act", "ms_policy_act_common", "ms_policy_act_compact",
-    "ms_act_round_free", "ms_policy_act_greedy", "ms_act_round_greedy", "ms_price_table_build", "ms_act_frag_bytes", "ms_act_prepare", "ms_offer_act_free", "ms_discounted_returns", "ms_unit_returns",
+    "ms_act_round_free", "ms_policy_act_greedy", "ms_act_round_greedy", "ms_policy_evaluate", "ms_price_table_build", "ms_act_frag_bytes", "ms_act_prepare", "ms_offer_act_free", "ms_discounted_returns", "ms_unit_returns",
     "ms_ppo_workspace_bytes", "ms_ppo_grad", "ms_adam_step", "ms_adam_step_dev",
     "ms_aggregate_obs", "ms_decode_aggregated", "ms_dqn_act", "ms_dqn_workspace_bytes", "ms_dqn_grad",
     "ms_regen_agent_rows", "ms_bdqn_workspace_bytes", "ms_bdqn_prepare", "ms_bdqn_layer1_scratch_bytes", "ms_bdqn_layer1_compact",

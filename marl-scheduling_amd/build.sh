@@ -17,7 +17,7 @@ HEADERS=("${HERE}"/csrc/*.h "${HERE}/../include/marlsched.h")  # every header: o
 CCVER="$("${HIPCC}" --version 2>/dev/null | head -3 | tr '\n' ' ')"
 objs=()
 pids=()
-for src in env_kernels.hip acc_fill_kernels.hip policy_kernels.hip act_pair_kernels.hip greedy_kernels.hip returns_kernels.hip ppo_kernels.hip agg_kernels.hip dqn_kernels.hip bdqn_kernels.hip bdqn_update_kernels.hip wide_kernels.hip snapshot_kernels.hip capi.cpp; do
+for src in env_kernels.hip acc_fill_kernels.hip policy_kernels.hip act_pair_kernels.hip greedy_kernels.hip evaluate_kernels.hip returns_kernels.hip ppo_kernels.hip agg_kernels.hip dqn_kernels.hip bdqn_kernels.hip bdqn_update_kernels.hip wide_kernels.hip snapshot_kernels.hip capi.cpp; do
   obj="${OBJDIR}/${src%.*}.o"
   # the env round reproduces Python's float64 arithmetic: no contraction there; the policy
   # and PPO kernels follow torch's f32 (which fuses freely) within tolerance: fma allowed
@@ -26,6 +26,10 @@ for src in env_kernels.hip acc_fill_kernels.hip policy_kernels.hip act_pair_kern
   # the gradient kernel's variants (common rows by bytes or by owners) must agree bit for bit: fma only
   # where an expression asks for it, never across statements (fast contraction depends on the code around)
   [[ "${src}" == ppo_kernels.hip || "${src}" == bdqn_kernels.hip || "${src}" == wide_kernels.hip ]] && contract=(-ffp-contract=on)
+  # the evaluation kernel (log-prob, value, entropy) takes the forward from the acting headers, which contract
+  # freely under their own pragma and so round as k_act does; its own softmax tail and entropy sum fuse only where
+  # an expression says so (on), so an output does not depend on which others the caller asked for
+  [[ "${src}" == evaluate_kernels.hip ]] && contract=(-ffp-contract=on)
   # cfg3's paired acting kernel is a latency-bound chain: the ILP-first machine scheduler shortens it
   # (rollout 12.14 -> 11.88 ms, profiles/r3f2/ab_sched_ilp_act.txt); the env round gains nothing, and the
   # gradient, returns and the other acting kernels (k_act / k_act_common, cfg4) lose with it, so they keep the

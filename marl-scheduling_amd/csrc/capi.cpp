@@ -16,6 +16,7 @@
 #include "ms_layout.h"
 #include "ms_env_launch.h"
 #include "ms_act_args.h"
+#include "ms_evaluate.h"
 #include "ms_returns.h"
 #include "ms_dqn.h"
 #include "ms_bdqn.h"
@@ -971,6 +972,36 @@ int ms_policy_act_greedy(const ms_mlp_params* p, const int8_t* obs, int32_t obs_
     ms::GreedyArgs a = act_shape<ms::GreedyArgs>(p, obs, obs_stride, n_envs, n_units, units_per_group);
     a.common = common_row, a.action = action, a.logprob = logprob;
     return greedy_rc(ms::dispatch_greedy(a, (hipStream_t)stream), "ms_policy_act_greedy");
+}
+
+int ms_policy_evaluate(const ms_mlp_params* actor, const ms_mlp_params* critic, const int8_t* obs, int32_t obs_stride,
+                       int64_t n_envs, int32_t n_units, int32_t units_per_group, const int8_t* actions, float* logprob,
+                       float* value, float* entropy, void* stream) {
+    if (!obs) return fail(MS_EINVAL, "ms_policy_evaluate: obs is NULL");
+    int rc = check_mlp(actor, obs_stride, n_units, units_per_group);
+    if (rc) return rc;
+    if (n_envs < 1) return fail(MS_EINVAL, "n_envs must be >= 1");
+    if (logprob && !actions) return fail(MS_EINVAL, "ms_policy_evaluate: logprob needs actions");
+    if (value && !critic) return fail(MS_EINVAL, "ms_policy_evaluate: value needs the critic");
+    if (critic) {
+        if (!critic->w1 || !critic->b1 || !critic->w2 || !critic->b2 || !critic->w3 || !critic->b3)
+            return fail(MS_EINVAL, "ms_policy_evaluate: NULL critic weight");
+        if (critic->hidden != 16) return fail(MS_EINVAL, "critic hidden width %d not built (16 only)", critic->hidden);
+        if (critic->n_actions != 1) return fail(MS_EINVAL, "ms_policy_evaluate: the critic's output width must be 1");
+        if (critic->in_dim != actor->in_dim || critic->n_groups != actor->n_groups)
+            return fail(MS_EINVAL, "ms_policy_evaluate: the critic's in_dim / n_groups (%d / %d) differ from the actor's (%d / %d)",
+                        critic->in_dim, critic->n_groups, actor->in_dim, actor->n_groups);
+    }
+    ms::EvalArgs a{};
+    a.actor = *actor, a.obs = obs, a.stride = obs_stride, a.U = n_units, a.S = units_per_group;
+    if (value) a.critic = *critic;
+    a.E = n_envs * (int64_t)n_units <= 0x7fffffffll ? (int)n_envs : 0, a.n_items = a.E * a.S;
+    a.actions = actions, a.logprob = logprob, a.value = value, a.entropy = entropy;
+    const hipError_t e = ms::dispatch_evaluate(a, (hipStream_t)stream);
+    if (e == hipErrorInvalidValue)
+        return fail(MS_EINVAL, "ms_policy_evaluate: shape not built (hidden 16, A <= 127, stride <= 256, rows * stride < 2^31)");
+    if (e != hipSuccess) return fail(MS_EHIP, "ms_policy_evaluate: %s", hipGetErrorString(e));
+    return MS_OK;
 }
 
 int ms_act_round_greedy(const ms_mlp_params* core, const ms_mlp_params* price, const int8_t* off_obs, int32_t off_stride,

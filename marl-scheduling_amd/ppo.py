@@ -216,6 +216,39 @@ class GroupedActorCritic(nn.Module):
                                        ptr(action), ptr(logprob), stream_ptr(stream)))
         return action, logprob
 
+    @torch.no_grad()
+    def evaluate_hip(self, obs_i8, actions_i8, n_units: int, logprob=None, value=None, entropy=None, stream=None,
+                     want=("logprob", "value", "entropy")):
+        """``evaluate`` (ActorCritic.evaluate, PPOmodules.py:65-72) on the HIP kernel (ms_policy_evaluate) for obs
+        [E, n_units, stride] int8 and actions [E, n_units] int8: the log-prob of the given action (log of the
+        probability clamped to [eps, 1 - eps], what ``act`` writes for its sample), the critic's value and the
+        entropy, each f32 [E, U]. Unit u uses group u // (n_units // G). An output is written into the tensor
+        given for it or into a new one; ``want`` names the outputs to compute when no tensor is given (an output
+        left out is None and is not computed; without "value" the critic is not read). An action outside
+        [0, A) gives NaN in logprob. No random number is drawn. Returns (logprob, value, entropy)."""
+        if not has("ms_policy_evaluate"):
+            raise RuntimeError("the loaded libmarlsched.so has no ms_policy_evaluate (built before it)")
+        E, U, stride = obs_i8.shape
+        assert U == n_units and U % self.G == 0 and obs_i8.dtype == torch.int8 and obs_i8.is_contiguous()
+        dev = obs_i8.device
+        outs = []
+        for name, t in (("logprob", logprob), ("value", value), ("entropy", entropy)):
+            if t is None and name in want:
+                t = torch.empty((E, U), dtype=torch.float32, device=dev)
+            if t is not None:
+                assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == E * U and t.device == dev
+            outs.append(t)
+        logprob, value, entropy = outs
+        if logprob is not None:
+            assert actions_i8 is not None and actions_i8.dtype == torch.int8 and actions_i8.is_contiguous()
+            assert actions_i8.numel() == E * U and actions_i8.device == dev
+        p = self.mlp_params()
+        c = self.critic_mlp_params() if value is not None else None
+        check(lib.ms_policy_evaluate(ct.byref(p), ct.byref(c) if c is not None else None, ptr(obs_i8), stride, E, U,
+                                     U // self.G, ptr(actions_i8), ptr(logprob), ptr(value), ptr(entropy),
+                                     stream_ptr(stream)))
+        return logprob, value, entropy
+
 
 class PriceTable:
     """The price chooser's sampling table (ms_price_table): the inputs the env can hand it are
@@ -530,6 +563,7 @@ class PPOGroup:
         self.gamma, self.eps_clip, self.K = gamma, eps_clip, k_epochs
         self.allreduce = allreduce
         self.last_losses = []
+        self.last_terms = None  # the last fused Trainer.update's loss terms [draws * K][G][3] (ms_ppo_grads.loss)
 
     @property
     def optimizer(self):

@@ -161,8 +161,13 @@ class Trainer:
     def __init__(self, cfg: abi.MsConfig, n_envs: int, arch: str = "local", hyper: Hyper | None = None, seed: int = 0,
                  device=None, rank: int = 0, world_size: int = 1, process_group=None, fused: bool = True,
                  use_graph: bool = True, common_rows: bool = True, rollout_streams: int = 1, metrics: bool = False,
-                 episode_length: int | None = None, compact: bool = True, hardcoded_agents=None):
-        """hardcoded_agents (an iterable of 0-based agent indices; fixed prices): train in a mixed market. The given
+                 episode_length: int | None = None, compact: bool = True, hardcoded_agents=None, diagnostics: int = 0):
+        """diagnostics (k >= 0): the number of ring slots update_diagnostics() evaluates after each update,
+        slots (2 i + 1) T // (2 k) for i < min(k, T); with k > 0 iteration() calls it after the update's end event
+        and appends the result to self.diagnostics_log. 0 (the default) is off: nothing is allocated or launched.
+        The log is not written into checkpoints (the checkpoint format does not know it): a resumed run starts an
+        empty one.
+        hardcoded_agents (an iterable of 0-based agent indices; fixed prices): train in a mixed market. The given
         agents play the reference's DividedHardcodedAgent rules inside the env kernel in every rollout round (as in
         evaluate(hardcoded_agents=...)), the action rings receive what they played, and they never train: no
         sub-unit of theirs is drawn for an update, and under ``local`` / ``divided`` their nets' groups are frozen
@@ -387,6 +392,18 @@ class Trainer:
             self.off_pair = torch.zeros((T + 1, self.E, N * L), dtype=torch.int16, device=dev)
         self._offers_pending = False
         self._fill_args = []
+        # update diagnostics (update_diagnostics): off unless asked for; the buffers are made at the first call
+        self.diagnostics = int(diagnostics)
+        if self.diagnostics < 0:
+            raise ValueError("diagnostics must be >= 0")
+        k = self.diagnostics
+        self.diagnostics_slots = [((2 * i + 1) * T) // (2 * k) for i in range(min(k, T))]
+        self.diagnostics_log = []
+        self._diag = None         # unit name -> the kept device tensors
+        self._diag_slot0 = None   # ring slot 0's observations as the rollout acted on them (the update's carry
+                                  # overwrites the rings' slot 0): kept only when slot 0 is among the default slots
+        self._diag_ready = False  # between an update() and the next rollout()
+        self._last_draws = None   # the last update's sub-unit draws on the host
         self.span_every = 0  # > 0: every span_every-th round's env launches record their span (bench)
         self.spans = None
         self.timings = dict(rollout=0.0, update=0.0)
@@ -744,6 +761,9 @@ class Trainer:
         first read (_complete_rings); otherwise the rings are complete when this returns."""
         self._rings_pending = False  # (rings of an earlier rollout nobody read: overwritten now)
         self._offers_pending = False
+        self._diag_ready = False
+        if 0 in self.diagnostics_slots:
+            self._keep_slot0()
         if not self.use_graph:
             self._rollout_body()
         elif self.graph is None:
@@ -769,6 +789,7 @@ class Trainer:
         dev = self.device if device is None else device
         if self.arch == "divided":
             sel = dict(acceptor=[torch.arange(N * C, device=dev)], offer=[torch.arange(N * L, device=dev)])
+            host = dict(acceptor=[list(range(N * C))], offer=[list(range(N * L))])
         elif self.arch == "local":
             acc = [[0] * N for _ in range(CS)]
             off = [[0] * N for _ in range(CS)]
@@ -785,8 +806,10 @@ class Trainer:
                     off[j][a] = a * L + self.rng.randint(0, L - 1)
             sel = dict(acceptor=[torch.tensor(r, device=dev) for r in acc],
                        offer=[torch.tensor(r, device=dev) for r in off])
+            host = dict(acceptor=[list(r) for r in acc], offer=[list(r) for r in off])
         else:
             acc, off = [], []
+            host = dict(acceptor=[], offer=[])
             # a mixed market: the agent is drawn among the learned ones (their rows alone hold sampled actions)
             agent = (lambda: self.learned[self.rng.randint(0, len(self.learned) - 1)]) if self.hc_mask else \
                 (lambda: self.rng.randint(0, N - 1))
@@ -794,12 +817,16 @@ class Trainer:
                 a = agent()
                 c = self.rng.randint(0, C - 1)
                 acc.append(torch.tensor([a * C + c], device=dev))
+                host["acceptor"].append([a * C + c])
             for _ in range(CS):  # SchedulingEnvironment.py:323-329
                 a = agent()
                 l = self.rng.randint(0, L - 1)
                 off.append(torch.tensor([a * L + l], device=dev))
+                host["offer"].append([a * L + l])
             sel = dict(acceptor=acc, offer=off)
         sel["price"] = sel["offer"]
+        host["price"] = host["offer"]
+        self._last_draws = host  # (update_diagnostics reads the rows the update drew)
         return sel
 
     def update(self):
@@ -811,12 +838,16 @@ class Trainer:
         copies of the graph's own tensors."""
         self._policy_version += 1  # policy_old changes: round() rebuilds the acting tables
         if self.use_graph and self.fused:
-            return self._update_graphed()
-        sel = self._draws()
-        if self.fused:
-            return self._fused_update({k: torch.cat(v).to(torch.int32) for k, v in sel.items()},
-                                      {k: [x.numel() for x in v] for k, v in sel.items()})
-        return self._torch_update(sel)
+            losses = self._update_graphed()
+        else:
+            sel = self._draws()
+            if self.fused:
+                losses = self._fused_update({k: torch.cat(v).to(torch.int32) for k, v in sel.items()},
+                                            {k: [x.numel() for x in v] for k, v in sel.items()})
+            else:
+                losses = self._torch_update(sel)
+        self._diag_ready = True  # until the next rollout() overwrites the rings
+        return losses
 
     def _update_rows(self, u):
         """(states, actions, old log-probs) of unit type u for ms_ppo_grad: [T*E, U(, stride)] rows, or
@@ -857,18 +888,20 @@ class Trainer:
             col += n
         if self.update_graph is None:
             losses = self._fused_update(views, self._sel_counts)  # this iteration's update
-            eager_last = {u.name: u.group.last_losses for u in self.units()}
+            eager_last = {u.name: (u.group.last_losses, u.group.last_terms) for u in self.units()}
             torch.cuda.synchronize(self.device)
             self._graph_losses = self._capture_update(views)
             self._graph_last = {u.name: list(u.group.last_losses) for u in self.units()}
+            self._graph_terms = {u.name: u.group.last_terms for u in self.units()}
             for u in self.units():  # the eager run's own losses until the first replay
-                u.group.last_losses = eager_last[u.name]
+                u.group.last_losses, u.group.last_terms = eager_last[u.name]
             return losses
         self._replay_update()
         # the graph's loss tensors are overwritten by every replay: hand out copies (G floats per
         # unit type), so losses a caller keeps from earlier iterations stay what they were
         for u in self.units():
             u.group.last_losses = [x.clone() for x in self._graph_last[u.name]]
+            u.group.last_terms = self._graph_terms[u.name]  # (the graph's own tensor: valid until the next replay)
         return {k: v.clone() for k, v in self._graph_losses.items()}
 
     def _capture_update(self, views):
@@ -938,6 +971,7 @@ class Trainer:
                 u.group.hip_optimizer.step()
         for u, _, ls in steps.values():
             losses[u.name] = self._mask_losses(u, combine_losses(terms[u.name]))
+            u.group.last_terms = terms[u.name]  # [draws * K][G][3] (a graph's own tensor under use_graph)
             u.group.last_losses = list(losses[u.name].unbind(0))
             u.group.sync_old()
         self._carry_last_observation()
@@ -985,6 +1019,7 @@ class Trainer:
                     ep.launch(terms[i])
                     u.group.hip_optimizer.step(st)
                 losses[u.name] = self._mask_losses(u, combine_losses(terms))
+                u.group.last_terms = terms  # [draws * K][G][3] (a graph's own tensor under use_graph)
                 u.group.last_losses = list(losses[u.name].unbind(0))
                 u.group.sync_old()
         for st in self._unit_streams:
@@ -1022,6 +1057,141 @@ class Trainer:
             self.acc_obs[0].copy_(self.acc_obs[self.T])
         self._off_obs[0].copy_(self._off_obs[self.T])  # (compact: the next rollout compresses slot 0 again)
 
+    # ---- update diagnostics
+    def _keep_slot0(self):
+        """Ring slot 0's observations before a rollout (eager copies, never inside a capture): the update's carry
+        writes the last observation over them, and update_diagnostics may be asked for slot 0 (2 k > T)."""
+        if self._diag_slot0 is None:
+            src = dict(off=self._off_obs[0])
+            if self.compact:
+                src.update(acc_rows=self.acc_rows[0], acc_owner=self.acc_owner[0])
+            else:
+                src.update(acc_obs=self.acc_obs[0])
+            self._diag_slot0 = {k: torch.empty_like(v) for k, v in src.items()}
+        d = self._diag_slot0
+        d["off"].copy_(self._off_obs[0])
+        if self.compact:
+            d["acc_rows"].copy_(self.acc_rows[0])
+            d["acc_owner"].copy_(self.acc_owner[0])
+        else:
+            d["acc_obs"].copy_(self.acc_obs[0])
+
+    def _diag_buffers(self, u, n_draws: int, n_slots: int):
+        """The kept tensors of unit type u's diagnostics, [draws][slots][E][G] rows: made once per shape."""
+        if self._diag is None:
+            self._diag = {}
+        b = self._diag.get(u.name)
+        G = u.group.policy.G
+        shape = (n_draws, n_slots, self.E, G)
+        if b is None or b["act"].shape != shape:
+            dev = self.device
+            f32 = lambda: torch.empty(shape, dtype=torch.float32, device=dev)
+            b = dict(obs=torch.zeros(shape + (u.stride,), dtype=torch.int8, device=dev),
+                     act=torch.empty(shape, dtype=torch.int8, device=dev), old=f32(), new=f32(), val=f32(), ent=f32(),
+                     sel=torch.empty((n_draws, G), dtype=torch.long, device=dev),
+                     sel32=torch.empty((n_draws * G,), dtype=torch.int32, device=dev))
+            self._diag[u.name] = b
+        return b
+
+    def diagnostics_bytes(self) -> int:
+        """Bytes of the kept diagnostic tensors (0 before the first update_diagnostics)."""
+        n = sum(t.numel() * t.element_size() for b in (self._diag or {}).values() for t in b.values())
+        return n + sum(t.numel() * t.element_size() for t in (self._diag_slot0 or {}).values())
+
+    @torch.no_grad()
+    def update_diagnostics(self, slots=None) -> dict:
+        """What the last update did to the policy, per unit type (acceptor, offer, and price under free prices) and
+        group: legal after update() and before the next rollout() (RuntimeError otherwise: the rings it reads belong
+        to the rollout the update consumed). For each group it takes the rows of every sub-unit the update drew for
+        it (all centralisation_sample draws, a sub-unit drawn twice counted twice), at ring slots `slots` (default:
+        diagnostics_slots), gathers them into explicit [rows][G][stride] rows (offer rows through off_obs, acceptor
+        rows regenerated from the core rows, the owners and the common row, price rows from the price ring; actions
+        and old log-probs through the completing accessors), evaluates the current `policy` on them with one
+        evaluate_hip call per unit type (ms_policy_evaluate) and reduces in float64 on the device. With
+        lr = new log-prob - old log-prob and Gt the normalised return the update trained on (unit_returns):
+          approx_kl = mean(-lr); approx_kl_k3 = mean(exp(lr) - 1 - lr); clip_fraction = the share of rows with
+          exp(lr) outside [1 - eps_clip, 1 + eps_clip]; ratio_max = max exp(lr); entropy = mean entropy;
+          value_mse = mean((V - Gt)^2); explained_variance = 1 - var(Gt - V) / var(Gt) (population variances; NaN
+          when var(Gt) == 0); rows = the number of rows reduced.
+        Returns {unit name: {value name: [G] list}, "slots": [...]}; a group frozen by hardcoded_agents reports
+        None. Several ranks: each rank reports its own rows. Slot 0 needs the copy a trainer with 0 among its
+        diagnostics_slots keeps (ValueError otherwise). Every launch is eager on the current stream; nothing is
+        drawn from self.rng, no Philox counter, ring slot the next iteration reads or captured graph changes. The
+        results are not written into checkpoints."""
+        if not self._diag_ready or self._last_draws is None:
+            raise RuntimeError("update_diagnostics() is legal after update() and before the next rollout()")
+        if capturing():
+            raise RuntimeError("update_diagnostics() inside a stream capture")
+        T, E, C = self.T, self.E, self.C
+        slots = list(self.diagnostics_slots if slots is None else slots)
+        if not slots or any(int(t) != t or not 0 <= t < T for t in slots):
+            raise ValueError("slots must be ring slots in [0, %d)" % T)
+        slots = [int(t) for t in slots]
+        if 0 in slots and self._diag_slot0 is None:
+            raise ValueError("ring slot 0 was overwritten by the update's carry: build the trainer with a "
+                             "diagnostics value whose slots include 0")
+        out = dict(slots=slots)
+        eps = float(self.hp.eps_clip)
+        dev = self.device
+        gather = torch.ops.aten.index.Tensor_out  # x[idx] into a kept tensor
+        i32 = torch.int32  # (rows move as dwords: every stride is a multiple of 4)
+        slot_idx = torch.tensor(slots, dtype=torch.long, device=dev).view(1, -1, 1, 1)
+        e_idx = torch.arange(E, device=dev).view(1, 1, E, 1)
+        pending = []
+        for u in self.units():
+            draws = self._last_draws[u.name]
+            G, n_d = u.group.policy.G, len(draws)
+            b = self._diag_buffers(u, n_d, len(slots))
+            b["sel"].copy_(torch.tensor(draws, dtype=torch.long))
+            b["sel32"].copy_(b["sel"].view(-1))
+            sel = b["sel"].view(n_d, 1, 1, G)
+            idx = [slot_idx, e_idx, sel]  # [draws][slots][E][G]: ring slot, replica, the draw's sub-unit of the group
+            actions, logprobs = u.actions, u.logprobs  # (completes the acceptor rings)
+            ret_all = unit_returns(u.rewards, b["sel32"], u.group.gamma)  # [T][E][draws * G], as the update's
+            if u is self.acc and self.compact:
+                # unit a * C + c: core row c where agent a + 1 owns the core, else the common row
+                core = (slot_idx, e_idx, sel % C)
+                mine = (self.acc_owner[core] == (sel // C + 1).to(torch.int8)).unsqueeze(-1)
+                torch.where(mine, self.acc_rows.view(i32)[core], self.acc_common.view(i32), out=b["obs"].view(i32))
+            else:
+                src = self.acc_obs if u is self.acc else (self.off_obs if u is self.off else self.price_obs)
+                gather(src.view(i32), idx, out=b["obs"].view(i32))  # (off_obs completes the offer rows)
+            if 0 in slots and u is not self.price:  # the rings' slot 0 holds the carried observation: the kept copy
+                k0, i = self._diag_slot0, slots.index(0)
+                for d in range(n_d):
+                    if u is self.acc and self.compact:
+                        c, a1 = b["sel"][d] % C, (b["sel"][d] // C + 1).to(torch.int8)
+                        own = (k0["acc_owner"].index_select(1, c) == a1).unsqueeze(-1)
+                        b["obs"][d, i].copy_(torch.where(own, k0["acc_rows"].index_select(1, c), self.acc_common))
+                    else:
+                        b["obs"][d, i].copy_(k0["acc_obs" if u is self.acc else "off"].index_select(1, b["sel"][d]))
+            gather(actions, idx, out=b["act"])
+            gather(logprobs, idx, out=b["old"])
+            col = (torch.arange(n_d, device=dev) * G).view(n_d, 1, 1, 1) + torch.arange(G, device=dev).view(1, 1, 1, G)
+            gt = ret_all[(slot_idx, e_idx, col)].view(-1, G).double()  # (a temporary, as ret_all itself)
+            R = n_d * len(slots) * E
+            u.group.policy.evaluate_hip(b["obs"].view(R, G, u.stride), b["act"].view(R, G), G, logprob=b["new"].view(R, G),
+                                        value=b["val"].view(R, G), entropy=b["ent"].view(R, G))
+            lr = b["new"].view(R, G).double() - b["old"].view(R, G).double()
+            ratio = torch.exp(lr)
+            v = b["val"].view(R, G).double()
+            var_gt = gt.var(0, unbiased=False)
+            pending.append((u, R, torch.stack([
+                (-lr).mean(0), (ratio - 1.0 - lr).mean(0),
+                ((ratio < 1.0 - eps) | (ratio > 1.0 + eps)).double().mean(0), ratio.max(0).values,
+                b["ent"].view(R, G).double().mean(0), ((v - gt) ** 2).mean(0),
+                torch.where(var_gt > 0, 1.0 - (gt - v).var(0, unbiased=False) / var_gt,
+                            torch.full_like(var_gt, float("nan")))])))
+        names = ("approx_kl", "approx_kl_k3", "clip_fraction", "ratio_max", "entropy", "value_mse", "explained_variance")
+        for u, R, res in pending:  # (the first .tolist() waits for the device; every unit type is queued by then)
+            res = res.tolist()
+            G = u.group.policy.G
+            frozen = set(self._frozen[u.name].tolist()) if u.name in self._frozen else set()
+            vals = {n: [None if g in frozen else res[j][g] for g in range(G)] for j, n in enumerate(names)}
+            vals["rows"] = [None if g in frozen else R for g in range(G)]
+            out[u.name] = vals
+        return out
+
     def iteration(self):
         """One PPO iteration; device time of rollout / update accumulates in self.timings (s)."""
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
@@ -1032,6 +1202,8 @@ class Trainer:
         ev[2].record()
         self._pending_events.append(ev)
         self.iterations += 1
+        if self.diagnostics:  # after the update's end event: the rollout and update spans do not see it
+            self.diagnostics_log.append(self.update_diagnostics())
         if self.metric_bufs is not None:
             self._harvest_episodes()
         return losses
@@ -1236,6 +1408,7 @@ class Trainer:
         arguments (ValueError naming the first differing manifest field; the trainer is left as it was). Works on
         a new trainer and on one that has already run. Returns the manifest."""
         from . import checkpoint
+        self._diag_ready = False  # (the rings no longer belong to an update of this trainer's)
         return checkpoint.load(self, path)
 
     def load_policy(self, path: str) -> dict:
