@@ -20,6 +20,7 @@
  *   ms_policy_act_greedy, ms_act_round_greedy <- the same forward with torch.argmax for the sample
  *                      (evaluating a trained policy; no counterpart in the reference's drivers)
  *   ms_policy_evaluate <- ActorCritic.evaluate             PPOmodules.py:65-72
+ *   ms_action_hist  <- the action logging of trainPPOExperiment3.py:215-237, as histograms per unit
  *   ms_discounted_returns, ms_unit_returns <- PPO.update return estimate  PPOmodules.py:128-137
  *
  * Conventions: plain pointers and sizes; every device pointer is a HIP device
@@ -478,6 +479,50 @@ int ms_policy_evaluate(const ms_mlp_params* actor, const ms_mlp_params* critic,
                        const int8_t* obs, int32_t obs_stride, int64_t n_envs, int32_t n_units,
                        int32_t units_per_group, const int8_t* actions,
                        float* logprob, float* value, float* entropy, void* stream);
+
+/* Action histograms ("Handlungslogging", trainPPOExperiment3.py:165-172; detect with dlsym: MS_ABI_VERSION is
+ * unchanged): counts += how often each unit took each action, per episode, from the int8 actions a rollout or a round
+ * wrote. Integer counts: exact, and the same from run to run.
+ *   rows    r = t * n_envs + e for t < n_rounds; row r lands in slot ((round0 + t) / episode_length) % n_slots
+ *   counts  int64 [n_slots][n_bins][n_actions], added into and never zeroed (the caller zeroes a slot it has read)
+ *   actions element (r, u) at actions[r * row_stride + u * unit_stride] (bytes), so [T][E][U] rings (row_stride U,
+ *           unit_stride 1) and unit-major [U][T][E] rings (row_stride 1, unit_stride T * E) are read alike;
+ *           select is addressed the same way with its own pair of strides
+ * mode MS_HIST_ALL:   every (r, u), u < n_units, in bin u (n_bins = n_units); select unused.
+ * mode MS_HIST_GATED: (r, u) only where select[r][u] != 0, in bin u. For the price chooser, with the offer units'
+ *           core actions as the gate: its action on the dummy state, taken when the core action is 0, is no offer.
+ * mode MS_HIST_OWNER: select is core_owner [R][n_cores]; for every (r, c) with owner o > 0 the acceptor action of
+ *           agent o - 1 on core c, in bin (o - 1) * n_cores + c (n_bins = n_agents * n_cores); cores of the
+ *           auctioneer (o == 0) are skipped. by_unit 0: actions is by core, [R][n_cores] (the one-launch rollout's
+ *           own_action); by_unit 1: actions is a ring by unit, [R][n_agents * n_cores], read at unit
+ *           (o - 1) * n_cores + c. n_units is ignored.
+ * An action outside [0, n_actions) and an owner outside [0, n_agents] are not binned and form no index; each such
+ * element adds one to *bad (int64 on the device, optional). An element that is not selected (gate 0, owner 0, or an
+ * owner out of range) has its action byte not examined.
+ * MS_EINVAL with a message, nothing launched and counts untouched: n_actions outside [1, 64], n_bins * n_actions
+ * above 16383 (the counters a workgroup keeps), n_envs, n_rounds, episode_length, n_slots or a stride < 1,
+ * round0 < 0, n_agents outside [1, 127] (owner mode), an unknown mode, actions or counts NULL, select NULL where the
+ * mode reads it. The arrays must hold n_rounds * n_envs rows at their strides (the kernel does not see their sizes). */
+#define MS_HIST_ALL 0
+#define MS_HIST_GATED 1
+#define MS_HIST_OWNER 2
+typedef struct ms_action_hist_args {
+    const int8_t* actions;
+    int64_t row_stride, unit_stride;
+    const int8_t* select;
+    int64_t select_row_stride, select_unit_stride;
+    int32_t mode;       /* MS_HIST_* */
+    int32_t by_unit;    /* owner mode only */
+    int32_t n_units;    /* all / gated */
+    int32_t n_agents, n_cores; /* owner mode */
+    int32_t n_actions;
+    int64_t n_envs;
+    int64_t round0;     /* the first row's round */
+    int32_t n_rounds, episode_length, n_slots, reserved;
+    int64_t* counts;
+    int64_t* bad;       /* or NULL */
+} ms_action_hist_args;
+int ms_action_hist(const ms_action_hist_args* args, void* stream);
 
 /* One round's getActionForAllAgents (SchedulingEnvironment.py:150-172), greedy, in one launch (two for shapes
  * without a paired kernel), on the observations ms_env_step emits: offer rows + compact acceptor rows

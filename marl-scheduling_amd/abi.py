@@ -240,6 +240,18 @@ class MsOfferCompact(ct.Structure):  # ms_offer_compact: the first round's templ
     _fields_ = [("tmpl", ct.c_void_p), ("pair", ct.c_void_p), ("tmpl_stride", ct.c_int64), ("pair_stride", ct.c_int64)]
 
 
+HIST_ALL, HIST_GATED, HIST_OWNER = 0, 1, 2  # MS_HIST_*
+
+
+class MsActionHistArgs(ct.Structure):  # ms_action_hist_args
+    _fields_ = [("actions", ct.c_void_p), ("row_stride", ct.c_int64), ("unit_stride", ct.c_int64),
+                ("select", ct.c_void_p), ("select_row_stride", ct.c_int64), ("select_unit_stride", ct.c_int64),
+                ("mode", ct.c_int32), ("by_unit", ct.c_int32), ("n_units", ct.c_int32), ("n_agents", ct.c_int32),
+                ("n_cores", ct.c_int32), ("n_actions", ct.c_int32), ("n_envs", ct.c_int64), ("round0", ct.c_int64),
+                ("n_rounds", ct.c_int32), ("episode_length", ct.c_int32), ("n_slots", ct.c_int32),
+                ("reserved", ct.c_int32), ("counts", ct.c_void_p), ("bad", ct.c_void_p)]
+
+
 class MsQnetParams(ct.Structure):
     _fields_ = [("w1", ct.c_void_p), ("b1", ct.c_void_p), ("w2", ct.c_void_p), ("b2", ct.c_void_p),
                 ("in_dim", ct.c_int32), ("hidden", ct.c_int32), ("n_actions", ct.c_int32), ("n_groups", ct.c_int32)]

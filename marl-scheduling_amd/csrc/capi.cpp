@@ -17,6 +17,7 @@
 #include "ms_env_launch.h"
 #include "ms_act_args.h"
 #include "ms_evaluate.h"
+#include "ms_action_hist.h"
 #include "ms_returns.h"
 #include "ms_dqn.h"
 #include "ms_bdqn.h"
@@ -1001,6 +1002,45 @@ int ms_policy_evaluate(const ms_mlp_params* actor, const ms_mlp_params* critic, 
     if (e == hipErrorInvalidValue)
         return fail(MS_EINVAL, "ms_policy_evaluate: shape not built (hidden 16, A <= 127, stride <= 256, rows * stride < 2^31)");
     if (e != hipSuccess) return fail(MS_EHIP, "ms_policy_evaluate: %s", hipGetErrorString(e));
+    return MS_OK;
+}
+
+int ms_action_hist(const ms_action_hist_args* g, void* stream) {
+    auto bad = [&](const char* why) { return fail(MS_EINVAL, "ms_action_hist: %s", why); };
+    if (!g) return bad("args is NULL");
+    if (!g->actions || !g->counts) return bad("actions / counts is NULL");
+    if (g->mode != MS_HIST_ALL && g->mode != MS_HIST_GATED && g->mode != MS_HIST_OWNER) return bad("unknown mode");
+    if (g->mode != MS_HIST_ALL && !g->select) return bad("the mode reads select, which is NULL");
+    if (g->n_actions < 1 || g->n_actions > ms::kHistMaxActions)
+        return fail(MS_EINVAL, "ms_action_hist: n_actions %d outside [1, %d]", g->n_actions, ms::kHistMaxActions);
+    if (g->n_envs < 1 || g->n_rounds < 1 || g->episode_length < 1 || g->n_slots < 1)
+        return bad("n_envs, n_rounds, episode_length and n_slots must be >= 1");
+    if (g->round0 < 0) return bad("round0 must be >= 0");
+    if (g->row_stride < 1 || g->unit_stride < 1) return bad("strides must be >= 1");
+    if (g->mode != MS_HIST_ALL && (g->select_row_stride < 1 || g->select_unit_stride < 1))
+        return bad("select strides must be >= 1");
+    ms::ActionHist a{};
+    a.mode = g->mode, a.by_unit = g->by_unit != 0;
+    if (g->mode == MS_HIST_OWNER) {
+        if (g->n_agents < 1 || g->n_agents > 127 || g->n_cores < 1) return bad("owner mode needs n_agents in [1, 127] and n_cores >= 1");
+        a.n_agents = g->n_agents, a.n_cores = a.n_cols = g->n_cores;
+    } else {
+        if (g->n_units < 1) return bad("n_units must be >= 1");
+        a.n_cols = g->n_units;
+    }
+    const int64_t bins = g->mode == MS_HIST_OWNER ? (int64_t)g->n_agents * g->n_cores : (int64_t)g->n_units;
+    if (bins * g->n_actions > ms::kHistMaxCounters)
+        return fail(MS_EINVAL, "ms_action_hist: %lld bins x %d actions do not fit the %d counters a workgroup keeps",
+                    (long long)bins, g->n_actions, ms::kHistMaxCounters);
+    a.n_bins = (int)bins, a.n_actions = g->n_actions;
+    a.actions = g->actions, a.row_stride = g->row_stride, a.unit_stride = g->unit_stride;
+    a.select = g->select, a.sel_row_stride = g->select_row_stride, a.sel_unit_stride = g->select_unit_stride;
+    a.E = g->n_envs, a.n_rounds = g->n_rounds, a.episode_length = g->episode_length, a.n_slots = g->n_slots;
+    a.round0 = g->round0;
+    a.counts = reinterpret_cast<unsigned long long*>(g->counts), a.bad = reinterpret_cast<unsigned long long*>(g->bad);
+    const hipError_t e = ms::launch_action_hist(a, (hipStream_t)stream);
+    if (e == hipErrorInvalidValue) return bad("too many rows for one launch");
+    if (e != hipSuccess) return fail(MS_EHIP, "ms_action_hist: %s", hipGetErrorString(e));
     return MS_OK;
 }
 

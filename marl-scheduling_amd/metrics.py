@@ -129,3 +129,35 @@ def save_args_dict(d: dict, file_name: str = "data{}.pkl", directory: str = ".")
     with open(path, "wb") as f:
         pickle.dump(d, f)
     return path
+
+
+# ---- action histograms (ppo.action_hist): integer counts [..., bins, n_actions]; an action log is a list of episodes,
+# each dict(offer [N, L, C+1], price [N, L, P] or None, acceptor [N, C, O+1], rounds, n_envs)
+def action_means(hist) -> np.ndarray:
+    """The exact mean action of every bin of an integer histogram [..., n_actions] (counts of actions
+    0 .. n_actions - 1): an object array of hist.shape[:-1] holding a Fraction per bin, None for an empty bin."""
+    h = np.asarray(hist)
+    out = np.empty(h.shape[:-1], dtype=object)
+    for i in np.ndindex(*h.shape[:-1]):
+        row = [int(c) for c in h[i]]
+        n = sum(row)
+        out[i] = Fraction(sum(a * c for a, c in enumerate(row)), n) if n else None
+    return out
+
+
+def action_args(action_log: list, agent: int = 0, collection_length: int | None = None) -> dict:
+    """Experiment 3's action keys (trainPPOExperiment3.py:215-237, 360-367) from an action log: key str(s), for every
+    offer slot s of `agent`, the list over episodes of the mean offer action of that slot, as statistics.mean gives
+    it over the episode's rounds (an int where the mean is whole, else the nearest float; None for an episode without
+    a count). With several replicas the mean is over all of them: the histograms are pooled. collection_length
+    names the keys of an empty log (otherwise read from the first episode)."""
+    if not action_log and collection_length is None:
+        return {}
+    L = int(collection_length) if collection_length is not None else np.asarray(action_log[0]["offer"]).shape[1]
+    out = {str(s): [] for s in range(L)}
+    for ep in action_log:
+        means = action_means(np.asarray(ep["offer"])[agent])
+        for s in range(L):
+            m = means[s]
+            out[str(s)].append(None if m is None else int(m) if m.denominator == 1 else float(m))
+    return out

@@ -387,6 +387,61 @@ def act_round_greedy(core: GroupedActorCritic, price: GroupedActorCritic | None,
                                   ptr(acc_action), stream_ptr(stream)))
 
 
+def _hist_rows(x, name):
+    """(row stride, unit stride) in bytes of an int8 [T, E, U] (or [E, U]) tensor whose rows r = t * E + e are evenly
+    spaced: contiguous rings, their slices over t, and the [T, E, U] views of unit-major [U, T, E] rings."""
+    assert x.dtype == torch.int8 and x.dim() == 3 and x.numel() > 0, name
+    T, E, U = x.shape
+    rs, us = x.stride(1), x.stride(2)
+    assert (T == 1 or x.stride(0) == E * rs) and rs >= 1 and us >= 1, name
+    return rs, us
+
+
+@torch.no_grad()
+def action_hist(actions, counts, round0: int, episode_length: int, gate=None, owner=None, n_agents: int | None = None,
+                bad=None, stream=None):
+    """counts += the per-episode histogram of int8 actions (ms_action_hist): actions [T, E, U] (or [E, U]: one
+    round), counts int64 [n_slots, n_bins, n_actions]; round t of the call is round round0 + t of the run and lands
+    in slot ((round0 + t) // episode_length) % n_slots. Exact (integers), never zeroes counts.
+    Neither gate nor owner: every element, bin u. gate [T, E, U] int8: only where gate != 0, bin u (the price
+    chooser's actions under the offer units' core actions). owner [T, E, C] int8 with n_agents: for every core with
+    owner o > 0 the acceptor action of agent o - 1, bin (o - 1) * C + c; actions is then by core [T, E, C] (the
+    one-launch rollout's own_action) or by unit [T, E, n_agents * C]. bad (int64 [1], optional) += the elements out
+    of range, which are not binned. The tensors may be strided views (unit-major rings)."""
+    if not has("ms_action_hist"):
+        raise RuntimeError("the loaded libmarlsched.so has no ms_action_hist (built before it)")
+    assert gate is None or owner is None
+    if actions.dim() == 2:
+        actions = actions.unsqueeze(0)
+        gate = gate.unsqueeze(0) if gate is not None else None
+        owner = owner.unsqueeze(0) if owner is not None else None
+    T, E, U = actions.shape
+    assert counts.dtype == torch.int64 and counts.is_contiguous() and counts.dim() == 3
+    n_slots, n_bins, A = counts.shape
+    g = abi.MsActionHistArgs()
+    g.actions, (g.row_stride, g.unit_stride) = ptr(actions), _hist_rows(actions, "actions")
+    g.mode, g.n_units, g.n_actions = abi.HIST_ALL, U, A
+    if gate is not None:
+        assert gate.shape == actions.shape
+        g.mode, g.select = abi.HIST_GATED, ptr(gate)
+        g.select_row_stride, g.select_unit_stride = _hist_rows(gate, "gate")
+    if owner is not None:
+        C = owner.shape[2]
+        assert owner.shape == (T, E, C) and n_agents is not None and U in (C, n_agents * C)
+        g.mode, g.select, g.n_agents, g.n_cores = abi.HIST_OWNER, ptr(owner), int(n_agents), C
+        g.select_row_stride, g.select_unit_stride = _hist_rows(owner, "owner")
+        g.by_unit = int(U != C)
+        assert n_bins == n_agents * C
+    else:
+        assert n_bins == U
+    g.n_envs, g.round0, g.n_rounds, g.episode_length, g.n_slots = E, int(round0), T, int(episode_length), n_slots
+    g.counts = ptr(counts)
+    if bad is not None:
+        assert bad.dtype == torch.int64 and bad.numel() == 1
+        g.bad = ptr(bad)
+    check(lib.ms_action_hist(ct.byref(g), stream_ptr(stream)))
+
+
 def _check_price_out(out, E: int, U: int, pus: int):
     """The price chooser's outputs: [E, U(, 4)] contiguous (pus = 0), or unit-major [U, E(, 4)] views
     whose unit stride (in rows) is pus."""
