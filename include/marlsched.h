@@ -19,6 +19,7 @@
  *   ms_policy_act   <- PPO.selectAction / ActorCritic.act  PPOmodules.py:53-63,114-125
  *   ms_policy_act_greedy, ms_act_round_greedy <- the same forward with torch.argmax for the sample
  *                      (evaluating a trained policy; no counterpart in the reference's drivers)
+ *   ms_wide_act_greedy <- the same for the aggregated agents' nets (ms_wide_act's forward)
  *   ms_policy_evaluate <- ActorCritic.evaluate             PPOmodules.py:65-72
  *   ms_action_hist  <- the action logging of trainPPOExperiment3.py:215-237, as histograms per unit
  *   ms_discounted_returns, ms_unit_returns <- PPO.update return estimate  PPOmodules.py:128-137
@@ -835,6 +836,16 @@ int ms_decode_aggregated(const ms_config* cfg, int64_t n_envs, const int32_t* ac
  * action / logprob [n_rows][G]. */
 int ms_wide_act(const ms_mlp_params* actor, const int8_t* obs, int32_t obs_stride, int64_t n_rows,
                 const float* uniforms, int32_t* action, float* logprob, void* stream);
+
+/* ms_wide_act_greedy: ms_wide_act's rows and forward with the argmax in place of the sample, for a
+ * deterministic evaluation of the aggregated nets: action[e][g] is the first maximum of the row's
+ * logits (the larger logit wins, the smaller action number on equal logits, in a fixed reduction
+ * order), always in [0, n_actions). No uniform is read and no random number drawn. logprob may be
+ * NULL (not computed); otherwise log(clamp(p_a, eps, 1 - eps)) in ms_wide_act's arithmetic. Shapes
+ * ms_wide_act refuses are refused the same way. An optional entry point of ABI 24 (a library built
+ * before it lacks the symbol). */
+int ms_wide_act_greedy(const ms_mlp_params* actor, const int8_t* obs, int32_t obs_stride, int64_t n_rows,
+                       int32_t* action, float* logprob, void* stream);
 
 typedef struct ms_wide_batch {
     const int8_t* states;      /* row r of group g at states + (r * G + g) * stride (the [T][E][N] rings, r = t*E + e) */

@@ -23,6 +23,7 @@ import torch
 
 from . import abi
 from .env import BatchedEnv
+from .episode_log import EpisodeLog, EpisodeLogging, check_evaluate_args, evaluation_result
 from .ppo import PPOGroup, discounted_returns, reference_actor_critic_params
 from .trainer import Hyper, env_seed
 
@@ -60,11 +61,15 @@ class _AggUnit:
         return torch.stack(losses)
 
 
-class AggregatedTrainer:
-    """The trainPPO.py loop (trainPPO.py:133-227) for aggregatedAgents / fullyAggregatedAgents."""
+class AggregatedTrainer(EpisodeLogging):
+    """The trainPPO.py loop (trainPPO.py:133-227) for aggregatedAgents / fullyAggregatedAgents.
+
+    metrics=True: every env round adds into the episode accumulators and the aggregated rewards' running sums
+    (episode_log.py); iteration() ends by appending the episodes finished by then to self.episode_log, for
+    args_dict() / save_args_dict(). Training is bit-identical with and without."""
 
     def __init__(self, cfg: abi.MsConfig, n_envs: int, fully: bool = False, hyper: Hyper | None = None, seed: int = 0,
-                 device=None):
+                 device=None, metrics: bool = False):
         if cfg.free_prices:
             raise ValueError("the aggregated envs are fixed-price only (SchedulingEnvironment.py:213-248)")
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
@@ -72,6 +77,7 @@ class AggregatedTrainer:
         self.cfg, self.E, self.fully = cfg, int(n_envs), bool(fully)
         self.hp = hp = hyper or Hyper()
         T = self.T = hp.update_step
+        self.seed = int(seed)
         self.env = BatchedEnv(cfg, self.E, seed=env_seed(seed, 0, self.E), device=self.device)
         env = self.env
         N, C, L = env.N, env.C, env.L
@@ -117,6 +123,11 @@ class AggregatedTrainer:
         env.reset(self.div_obs)
         self._aggregate(0)
         self.iterations = 0
+        self.rounds_done = 0
+        # as Trainer sizes them: the episodes a rollout of T rounds can touch, so none is reused unread
+        self.ep_len = int(cfg.episode_length)
+        self._init_episode_log(metrics, env, slots=-(-T // self.ep_len) + 1, aggregated=True,
+                               episodeLength=self.ep_len, UPDATE_STEP=T, n_envs=self.E)
 
     def _aggregate(self, t):
         out = {k: u.obs[t] for k, u in self.units.items()}
@@ -134,7 +145,10 @@ class AggregatedTrainer:
         # n_bad counts illegal action numbers over the iteration (reset at its start); the reference
         # raises on one (Agent.py:651-652): iteration() checks the count after the rollout
         acc, off = self.env.decode_aggregated(self.numbers, self.fully, n_bad=self.n_bad)
-        self.env.step(acc, off, obs=self.div_obs, rewards=self.rew)
+        self.env.step(acc, off, obs=self.div_obs, rewards=self.rew, events=self._metric_events)
+        if self._elog is not None:
+            self._elog.add_aggregated(self.rounds_done, self.rew["aggregated_acceptor"], self.rew["aggregated_offer"])
+        self.rounds_done += 1
         agent = self.rew["agent"].float()
         agg_off = self.rew["aggregated_offer"].float()
         if self.fully:  # PPOFullyAggregatedFixPriceEnv.saveRewards (SchedulingEnvironment.py:243-247)
@@ -159,7 +173,64 @@ class AggregatedTrainer:
             raise ValueError("Illegal Argument: %d action numbers outside the action space (Agent.py:651-652)"
                              % int(self.n_bad.item()))
         self.iterations += 1
-        return self.update()
+        losses = self.update()
+        if self._elog is not None:
+            self._elog.harvest(self.rounds_done)
+        return losses
+
+    # ---- evaluation
+    def eval_seed(self, n_envs: int | None = None) -> int:
+        """Default base seed of evaluate()'s replicas: the training env's base seed plus 500_001 (as
+        Trainer.eval_seed), so the evaluation replicas meet no training replica's job stream."""
+        return env_seed(self.seed, 0, int(n_envs or self.E)) + 500_001
+
+    @torch.no_grad()
+    def evaluate(self, episodes: int = 1, n_envs: int | None = None, mode: str = "greedy",
+                 seed: int | None = None) -> dict:
+        """Evaluate the current policy (policy_old, the nets the next rollout acts with) for `episodes` episodes
+        on n_envs (default: E) fresh replicas of their own; replica e is seeded seed + e (default eval_seed()).
+        The training env, rings, counters, n_bad and torch's default generators are neither read nor written;
+        equal arguments give equal results. Eager launches on the current stream.
+
+        mode "greedy": every net takes the first maximum of its logits (ms_wide_act_greedy; no random number);
+        mode "sample": the nets sample (ms_wide_act) at uniforms of a torch.Generator of the call's own, seeded
+        from `seed`; mode "hardcoded": the in-kernel rule-based agents, the baseline on the same job streams.
+        An action number outside the action space raises ValueError, as in iteration().
+
+        Returns Trainer.evaluate's dict(mode, seed, n_envs, episodes, per_replica), with the aggregated
+        drivers' acceptorRew / coreChooserRew / priceChooserRew / terminationRevenues (episode_log.py) in
+        every mode, so the values compare with this trainer's own episode_log."""
+        episodes, E = check_evaluate_args(episodes, n_envs, self.E, mode, ("greedy", "sample", "hardcoded"))
+        seed = self.eval_seed(E) if seed is None else int(seed)
+        dev, N = self.device, self.N
+        env = BatchedEnv(self.cfg, E, seed=seed, device=dev)
+        log = EpisodeLog(env, slots=episodes, aggregated=True)
+        div_obs = env.reset(env.obs_buffers())
+        rew = env.reward_buffers(aggregated=True)
+        agg = {k: torch.zeros((E, N, u.stride), dtype=torch.int8, device=dev) for k, u in self.units.items()}
+        numbers = torch.zeros((len(self.units), E, N), dtype=torch.int32, device=dev)
+        n_bad = torch.zeros(1, dtype=torch.int32, device=dev)
+        gen = torch.Generator(device=dev).manual_seed(seed) if mode == "sample" else None
+        acc_a = torch.zeros((E, N, env.C), dtype=torch.int8, device=dev)
+        off_a = torch.zeros((E, N, env.L), dtype=torch.int8, device=dev)
+        for t in range(episodes * self.ep_len):
+            if mode == "hardcoded":
+                acc = off = None
+            else:
+                env.aggregate_obs(div_obs, out=agg)
+                for i, (k, u) in enumerate(self.units.items()):  # acceptor, offer (or the fully aggregated net)
+                    if mode == "greedy":
+                        u.group.wide_act_greedy(agg[k], action=numbers[i], want_logprob=False)
+                    else:
+                        u.group.wide_act(agg[k], action=numbers[i], generator=gen)
+                acc, off = env.decode_aggregated(numbers, self.fully, acceptor=acc_a, offer_core=off_a, n_bad=n_bad)
+            env.step(acc, off, obs=div_obs, rewards=rew, events=log.events)
+            log.add_aggregated(t, rew["aggregated_acceptor"], rew["aggregated_offer"])
+        if int(n_bad.item()):
+            raise ValueError("Illegal Argument: %d action numbers outside the action space (Agent.py:651-652)"
+                             % int(n_bad.item()))
+        log.harvest(episodes * self.ep_len)
+        return evaluation_result(mode, seed, E, log.episodes)
 
     def flags(self) -> int:
         return self.env.flags()

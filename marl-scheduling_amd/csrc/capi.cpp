@@ -1850,6 +1850,29 @@ int ms_wide_act(const ms_mlp_params* a, const int8_t* obs, int32_t obs_stride, i
     return MS_OK;
 }
 
+int ms_wide_act_greedy(const ms_mlp_params* a, const int8_t* obs, int32_t obs_stride, int64_t n_rows, int32_t* action,
+                       float* logprob, void* stream) {
+    if (int rc = wide_check(a, "ms_wide_act_greedy")) return rc;
+    if (!obs || !action) return fail(MS_EINVAL, "ms_wide_act_greedy: NULL argument");
+    if (n_rows < 1 || obs_stride < a->in_dim || (obs_stride & 3))
+        return fail(MS_EINVAL, "ms_wide_act_greedy: n_rows >= 1 and obs_stride >= in_dim, multiple of 4");
+    if ((n_rows + 15) / 16 > 0x7fffffffLL || a->n_groups > 65535)
+        return fail(MS_EINVAL, "ms_wide_act_greedy: grid too large");
+    ms::WideGreedy p{};
+    p.actor = wide_net(a);
+    p.D = a->in_dim;
+    p.H = a->hidden;
+    p.A = a->n_actions;
+    p.G = a->n_groups;
+    p.obs = obs;
+    p.stride = obs_stride;
+    p.E = n_rows;
+    p.action = action;
+    p.logprob = logprob;  // NULL: not computed
+    HIP_TRY(ms::launch_wide_greedy(p, (hipStream_t)stream));
+    return MS_OK;
+}
+
 // work split and workspace layout of ms_wide_grad: NB row-tile blocks per group (k_wide_rows), RS
 // row splits of the weight-gradient reductions (partials [RS][G][total], at most 1 GiB)
 struct WidePlan {

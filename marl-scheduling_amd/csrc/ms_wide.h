@@ -30,6 +30,16 @@ struct WideAct {
     float* logprob;         // [E][G]
 };
 
+struct WideGreedy {
+    WideNet actor;
+    int D, H, A, G;
+    const int8_t* obs;  // row (e, g) at obs + (e * G + g) * stride
+    int stride;
+    long long E;
+    int32_t* action;    // [E][G]: the first maximum of the row's logits
+    float* logprob;     // [E][G], or NULL: not computed
+};
+
 // Offsets (floats) of one group's gradient in the flat partial vectors: o[i] for the tensors in
 // ms_ppo_grads order, o[kWideSegs] = the vector's length.
 enum { kOW1 = 0, kOB1, kOW2, kOB2, kOW3, kOB3, kOCW1, kOCB1, kOCW2, kOCB2, kOCW3, kOCB3, kWideSegs };
@@ -85,6 +95,8 @@ struct WideReduce {
 
 // the wide net's sampled actions, log-probs and values
 hipError_t launch_wide_act(const WideAct& p, hipStream_t st);
+// the wide net's argmax actions and (optionally) their log-probs; grid and LDS as launch_wide_act
+hipError_t launch_wide_greedy(const WideGreedy& p, hipStream_t st);
 // rows -> split partials -> gradient tensors (three launches on one stream)
 hipError_t launch_wide_grad(const WideRows& rows, const WideGrads& gp, const WideReduce& rp, hipStream_t st);
 

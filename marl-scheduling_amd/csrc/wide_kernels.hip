@@ -11,6 +11,11 @@
 //   k_wide_act     ActorCritic.act (PPOmodules.py:53-63): tanh MLP, softmax, Categorical sample at
 //                  a given uniform (the action is the number of running sums <= u * S) and its
 //                  log-prob log(clamp(p_a)), for rows (e, g) of [E][G][stride] int8 observations;
+//   k_wide_greedy  the same forward, the action the first maximum of the row's logits (argmax for a
+//                  deterministic evaluation): (value, index) pairs reduced in the chunk, across
+//                  the wave's lanes and across the four waves, the larger value winning and the
+//                  smaller index on equal values; no uniform read; the log-prob (optional) with
+//                  k_wide_act's sum pass;
 //   k_wide_rows    PPO.update's per-row work (PPOmodules.py:144-168): forward of actor and critic,
 //                  the softmax + Categorical renormalisation + clamped-log statistics, the loss
 //                  derivatives of -min(surr) + 0.5 MSE - 0.01 entropy, d logits (gz) and the
@@ -293,6 +298,122 @@ __global__ __launch_bounds__(TPB) void k_wide_act(WideAct p) {
         const long long o = (e0 + t) * p.G + g;
         p.action[o] = act;
         p.logprob[o] = logf(clampp(pe));
+    }
+}
+
+// (value, index) pairs ordered for the first maximum: the larger value wins, the smaller index on
+// equal values. A total order on the pairs met here (no NaN value: see k_wide_greedy), so folding
+// them in any grouping gives the same pair.
+__device__ __forceinline__ void first_max(float& v, int& i, float ov, int oi) {
+    if (ov > v || (ov == v && oi < i)) {
+        v = ov;
+        i = oi;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// k_wide_act's forward with the row's first maximum in place of the sample: no uniform is read.
+// LDS is carved as in k_wide_act (act_lds), the scan's slots unused.
+template <int H>
+__global__ __launch_bounds__(TPB) void k_wide_greedy(WideGreedy p) {
+    extern __shared__ float lds[];
+    constexpr int HP = pitch_h(H);
+    const int t = threadIdx.x, g = blockIdx.y, D = p.D, A = p.A;
+    const long long e0 = (long long)blockIdx.x * TR;
+    const int xp = pitch_x(D);
+    float* sx = lds;
+    float* sh1 = sx + up4(TR * xp);
+    float* sh2 = sh1 + TR * HP;
+    float* sM = sh2 + TR * HP;
+    float* sS = sM + TR;
+    float* red = sS + TR;  // [4][16]
+    int* ired = reinterpret_cast<int*>(red + 2 * 4 * TR);  // [4][16]
+    int* sAct = ired + 4 * TR;
+
+    const WideNet& n = p.actor;
+    const float* w3 = n.w3 + (size_t)g * A * H;
+    const float* b3 = n.b3 + (size_t)g * A;
+
+    load_rows(sx, xp, p.obs, e0, p.E, p.G, g, p.stride, D, t);
+    __syncthreads();
+    dense1<H>(n.w1 + (size_t)g * H * D, n.b1 + (size_t)g * H, D, sx, xp, sh1, HP, t);
+    __syncthreads();
+    dense1<H>(n.w2 + (size_t)g * H * H, n.b2 + (size_t)g * H, H, sh1, HP, sh2, HP, t);
+    __syncthreads();
+
+    int a0, a1;
+    chunk_of(A, t, a0, a1);
+    float w[H];
+    // pass 1: the chunk's first maximum per row. A NaN logit never compares greater, so m stays a
+    // number (or -inf) and idx an action of the chunk; an empty chunk holds (-inf, A - 1), which
+    // loses to every pair of a non-empty chunk
+    float m[TR];
+    int idx[TR];
+#pragma unroll
+    for (int r = 0; r < TR; r++) {
+        m[r] = -INFINITY;
+        idx[r] = a0 < A ? a0 : A - 1;
+    }
+    for (int a = a0; a < a1; a++) {
+        load_w<H>(w, w3 + (size_t)a * H);
+        const float b = b3[a];
+#pragma unroll
+        for (int r = 0; r < TR; r++) {
+            const float z = logit<H>(w, sh2 + r * HP, b);
+            if (z > m[r]) {
+                m[r] = z;
+                idx[r] = a;
+            }
+        }
+    }
+    // across the lanes of a wave, then the four waves in wave order
+#pragma unroll
+    for (int r = 0; r < TR; r++) {
+#pragma unroll
+        for (int s = 32; s >= 1; s >>= 1) {
+            const float ov = __shfl_xor(m[r], s, 64);
+            const int oi = __shfl_xor(idx[r], s, 64);
+            first_max(m[r], idx[r], ov, oi);
+        }
+    }
+    if ((t & 63) == 0)
+#pragma unroll
+        for (int r = 0; r < TR; r++) {
+            red[(t >> 6) * TR + r] = m[r];
+            ired[(t >> 6) * TR + r] = idx[r];
+        }
+    __syncthreads();
+    if (t < TR) {
+        float v = red[t];
+        int i = ired[t];
+        for (int q = 1; q < 4; q++) first_max(v, i, red[q * TR + t], ired[q * TR + t]);
+        sM[t] = v;
+        sAct[t] = i < 0 ? 0 : (i >= A ? A - 1 : i);
+    }
+    __syncthreads();
+    if (p.logprob) {  // (uniform over the block: block_red's barriers are met by every thread)
+        // k_wide_act's pass 2: chunk sums of exp(z - max) in action order, its block sum order
+        float s[TR];
+#pragma unroll
+        for (int r = 0; r < TR; r++) s[r] = 0.f;
+        for (int a = a0; a < a1; a++) {
+            load_w<H>(w, w3 + (size_t)a * H);
+            const float b = b3[a];
+#pragma unroll
+            for (int r = 0; r < TR; r++) s[r] += expf(logit<H>(w, sh2 + r * HP, b) - sM[r]);
+        }
+        block_red<float, TR, false>(s, red, sS, t);
+    }
+    if (t < TR && e0 + t < p.E) {
+        const int act = sAct[t];
+        const long long o = (e0 + t) * p.G + g;
+        p.action[o] = act;
+        if (p.logprob) {
+            load_w<H>(w, w3 + (size_t)act * H);
+            const float e = expf(logit<H>(w, sh2 + t * HP, b3[act]) - sM[t]);
+            const float pe = e * (1.f / sS[t]);
+            p.logprob[o] = logf(clampp(pe));
+        }
     }
 }
 
@@ -721,6 +842,18 @@ hipError_t launch_wide_act(const WideAct& p, hipStream_t st) {
         hipLaunchKernelGGL(k_wide_act<32>, grid, dim3(TPB), lds, st, p);
     else if (p.H == 64)
         hipLaunchKernelGGL(k_wide_act<64>, grid, dim3(TPB), lds, st, p);
+    else
+        return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
+hipError_t launch_wide_greedy(const WideGreedy& p, hipStream_t st) {
+    const dim3 grid((unsigned)((p.E + TR - 1) / TR), (unsigned)p.G);
+    const size_t lds = act_lds(p.H, p.D);
+    if (p.H == 32)
+        hipLaunchKernelGGL(k_wide_greedy<32>, grid, dim3(TPB), lds, st, p);
+    else if (p.H == 64)
+        hipLaunchKernelGGL(k_wide_greedy<64>, grid, dim3(TPB), lds, st, p);
     else
         return hipErrorInvalidValue;
     return hipGetLastError();

@@ -22,6 +22,7 @@ import torch.nn as nn
 
 from . import abi
 from ._lib import check, lib, ptr, stream_ptr
+from .episode_log import EpisodeLog, EpisodeLogging, check_evaluate_args, evaluation_result
 from .ppo import HipAdam
 
 HIDDEN = 16  # DQNEntity (DQNmodules.py:41-46)
@@ -195,7 +196,7 @@ class DQNGroup:
         return loss
 
 
-class DQNTrainer:
+class DQNTrainer(EpisodeLogging):
     """trainDQN.py:126-268 over E replicas of DQNDividedFixedPricesEnv (SchedulingEnvironment.py:428-436).
 
     One ``episode()`` = episodeLength rounds of: selectAction of every unit (offer nets, acceptor nets;
@@ -204,10 +205,15 @@ class DQNTrainer:
     (updateAcceptorMemoriesAndOptimize, updateOfferMemoriesAndOptimize :366-425). After episode i
     with i % TARGET_UPDATE == 0 the target nets are synced. Random streams: epsilon / exploration
     uniforms from Philox (per rank, round, unit), memory replacement indices and minibatch samples
-    from a torch device generator; the env stream stays the reference's per replica."""
+    from a torch device generator; the env stream stays the reference's per replica.
+
+    metrics=True: every env round adds into the episode accumulators (episode_log.py); when step_round()
+    returns done the episode's divided values (trainDQN.py:153-259) are appended to self.episode_log, for
+    args_dict() / save_args_dict(). Training is bit-identical with and without."""
 
     def __init__(self, cfg: abi.MsConfig, n_envs: int, hyper: DQNHyper | None = None, seed: int = 0, device=None,
-                 episode_length: int | None = None, rank: int = 0, world_size: int = 1, process_group=None):
+                 episode_length: int | None = None, rank: int = 0, world_size: int = 1, process_group=None,
+                 metrics: bool = False):
         from .env import BatchedEnv
         from .trainer import allreduce_mean_grads, env_seed
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
@@ -256,6 +262,8 @@ class DQNTrainer:
         self.seed = seed
         self.episodes = 0
         self.last_losses = {}
+        # one slot: an episode is read (and its slot zeroed) in the round that ends it
+        self._init_episode_log(metrics, self.env, slots=1, episodeLength=self.ep_len, n_envs=self.E * world_size)
 
     @property
     def round(self) -> int:
@@ -297,7 +305,8 @@ class DQNTrainer:
         self.off.policy.act(s["offer"], 1, eps, seed=key, offset=4 * r + 1, action=self.act_off)
         self.acc.policy.act(s["acceptor"], 1, eps, seed=key, offset=4 * r + 2, action=self.act_acc)
         obs_out = {k: v.view(E, N, -1, v.shape[-1]) for k, v in s1.items()}
-        self.env.step(self.act_acc.view(E, N, C), self.act_off.view(E, N, L), obs=obs_out, rewards=self.rew)
+        self.env.step(self.act_acc.view(E, N, C), self.act_off.view(E, N, L), obs=obs_out, rewards=self.rew,
+                      events=self._metric_events)
         done = self.round % self.ep_len == 0
         if not done and not self.hp.random_policy:
             self.mem_acc.push(s["acceptor"], self.act_acc, self.rew["acceptor"].view(E, N * C), s1["acceptor"],
@@ -306,6 +315,8 @@ class DQNTrainer:
                               self._replace_index(self.mem_off))
             self._optimize()
         self.cur = 1 - self.cur
+        if done and self._elog is not None:
+            self._elog.harvest(r + 1)
         return done
 
     def episode(self):
@@ -316,6 +327,48 @@ class DQNTrainer:
             self.acc.sync_target()
             self.off.sync_target()
         self.episodes += 1
+
+    # ---- evaluation
+    def eval_seed(self, n_envs: int | None = None) -> int:
+        """Default base seed of evaluate()'s replicas: the training env's base seed of this rank plus 500_001
+        (as Trainer.eval_seed), so the evaluation replicas meet no training replica's job stream."""
+        from .trainer import env_seed
+        return env_seed(self.seed, self.rank, int(n_envs or self.E)) + 500_001
+
+    @torch.no_grad()
+    def evaluate(self, episodes: int = 1, n_envs: int | None = None, mode: str = "greedy",
+                 seed: int | None = None) -> dict:
+        """Evaluate the policy nets for `episodes` episodes on n_envs (default: E) fresh replicas of their own;
+        replica e is seeded seed + e (default eval_seed()). The training env, the replay memories, the counters,
+        self.gen and torch's default generators are neither read nor written; equal arguments give equal
+        results. Eager launches on the current stream.
+
+        mode "greedy": every unit takes the first argmax of its Q values (ms_dqn_act's greedy output: no uniform
+        decides anything, and the Philox offset is a stateless argument); mode "hardcoded": the in-kernel
+        rule-based agents, the baseline on the same job streams.
+        Returns Trainer.evaluate's dict(mode, seed, n_envs, episodes, per_replica) of the divided values."""
+        from .env import BatchedEnv
+        episodes, E = check_evaluate_args(episodes, n_envs, self.E, mode, ("greedy", "hardcoded"))
+        seed = self.eval_seed(E) if seed is None else int(seed)
+        dev, N, C, L = self.device, self.N, self.C, self.L
+        env = BatchedEnv(self.cfg, E, seed=seed, device=dev)
+        log = EpisodeLog(env, slots=episodes)
+        s = env.shape
+        obs = dict(acceptor=torch.zeros((E, N, C, s.acc_obs_stride), dtype=torch.int8, device=dev),
+                   offer=torch.zeros((E, N, L, s.off_obs_stride), dtype=torch.int8, device=dev))
+        env.reset(obs)
+        rew = env.reward_buffers()
+        i8 = lambda u: torch.zeros((E, u), dtype=torch.int8, device=dev)
+        act_acc, act_off, g_acc, g_off = i8(N * C), i8(N * L), i8(N * C), i8(N * L)
+        for _ in range(episodes * self.ep_len):
+            if mode == "hardcoded":
+                env.step(None, None, obs=obs, rewards=rew, events=log.events)
+                continue
+            self.off.policy.act(obs["offer"].view(E, N * L, -1), 1, 0.0, action=act_off, greedy=g_off)
+            self.acc.policy.act(obs["acceptor"].view(E, N * C, -1), 1, 0.0, action=act_acc, greedy=g_acc)
+            env.step(g_acc.view(E, N, C), g_off.view(E, N, L), obs=obs, rewards=rew, events=log.events)
+        log.harvest(episodes * self.ep_len)
+        return evaluation_result(mode, seed, E, log.episodes)
 
     def flags(self) -> int:
         return self.env.flags()

@@ -658,6 +658,31 @@ class PPOGroup:
                               ptr(logprob), stream_ptr(stream)))
         return action, logprob
 
+    @torch.no_grad()
+    def wide_act_greedy(self, obs_i8, action=None, logprob=None, want_logprob=True, stream=None):
+        """wide_act with the argmax in place of the sample (ms_wide_act_greedy): row (e, g) of obs
+        [E, G, stride] int8 through group g's policy_old, the action the first maximum of its logits
+        (the smaller action number on equal logits); no random number is drawn. Returns (action int32
+        [E, G], log-prob f32 [E, G]), written into ``action`` / ``logprob`` when given. want_logprob
+        False: the log-prob is neither computed nor written (a given ``logprob`` is returned as it was,
+        else None)."""
+        if not has("ms_wide_act_greedy"):
+            raise RuntimeError("the loaded libmarlsched.so has no ms_wide_act_greedy (built before it)")
+        E, G, stride = obs_i8.shape
+        pol = self.policy_old
+        assert G == pol.G and obs_i8.dtype == torch.int8 and obs_i8.is_contiguous() and stride >= pol.D
+        dev = obs_i8.device
+        if action is None:
+            action = torch.empty((E, G), dtype=torch.int32, device=dev)
+        if logprob is None and want_logprob:
+            logprob = torch.empty((E, G), dtype=torch.float32, device=dev)
+        assert action.dtype == torch.int32 and action.is_contiguous() and action.shape == (E, G)
+        if logprob is not None:
+            assert logprob.dtype == torch.float32 and logprob.is_contiguous() and logprob.shape == (E, G)
+        check(lib.ms_wide_act_greedy(ct.byref(pol.mlp_params()), ptr(obs_i8), stride, E, ptr(action),
+                                     ptr(logprob if want_logprob else None), stream_ptr(stream)))
+        return action, logprob
+
     def wide_epoch(self, states_i8, actions_i32, old_logprobs, returns_gr, stream=None):
         """The gradient half of one K-epoch step of ``update_wide`` (ms_wide_grad): returns a function
         that writes the epoch's gradient into ``policy``'s .grad tensors and returns the per-group loss."""
