@@ -21,9 +21,9 @@ from __future__ import annotations
 
 import torch
 
-from . import abi
+from . import abi, evaluation
 from .env import BatchedEnv
-from .episode_log import EpisodeLog, EpisodeLogging, check_evaluate_args, evaluation_result
+from .episode_log import EpisodeLogging
 from .ppo import PPOGroup, discounted_returns, reference_actor_critic_params
 from .trainer import Hyper, env_seed
 
@@ -182,7 +182,7 @@ class AggregatedTrainer(EpisodeLogging):
     def eval_seed(self, n_envs: int | None = None) -> int:
         """Default base seed of evaluate()'s replicas: the training env's base seed plus 500_001 (as
         Trainer.eval_seed), so the evaluation replicas meet no training replica's job stream."""
-        return env_seed(self.seed, 0, int(n_envs or self.E)) + 500_001
+        return evaluation.eval_seed(self.seed, 0, int(n_envs or self.E))
 
     @torch.no_grad()
     def evaluate(self, episodes: int = 1, n_envs: int | None = None, mode: str = "greedy",
@@ -200,11 +200,9 @@ class AggregatedTrainer(EpisodeLogging):
         Returns Trainer.evaluate's dict(mode, seed, n_envs, episodes, per_replica), with the aggregated
         drivers' acceptorRew / coreChooserRew / priceChooserRew / terminationRevenues (episode_log.py) in
         every mode, so the values compare with this trainer's own episode_log."""
-        episodes, E = check_evaluate_args(episodes, n_envs, self.E, mode, ("greedy", "sample", "hardcoded"))
-        seed = self.eval_seed(E) if seed is None else int(seed)
-        dev, N = self.device, self.N
-        env = BatchedEnv(self.cfg, E, seed=seed, device=dev)
-        log = EpisodeLog(env, slots=episodes, aggregated=True)
+        episodes, seed, env, log = evaluation.fresh_env(self, episodes, n_envs, mode, ("greedy", "sample", "hardcoded"),
+                                                        seed, aggregated=True)
+        dev, N, E = self.device, self.N, env.E
         div_obs = env.reset(env.obs_buffers())
         rew = env.reward_buffers(aggregated=True)
         agg = {k: torch.zeros((E, N, u.stride), dtype=torch.int8, device=dev) for k, u in self.units.items()}
@@ -213,10 +211,10 @@ class AggregatedTrainer(EpisodeLogging):
         gen = torch.Generator(device=dev).manual_seed(seed) if mode == "sample" else None
         acc_a = torch.zeros((E, N, env.C), dtype=torch.int8, device=dev)
         off_a = torch.zeros((E, N, env.L), dtype=torch.int8, device=dev)
-        for t in range(episodes * self.ep_len):
-            if mode == "hardcoded":
-                acc = off = None
-            else:
+
+        def one_round(t):
+            acc = off = None
+            if mode != "hardcoded":
                 env.aggregate_obs(div_obs, out=agg)
                 for i, (k, u) in enumerate(self.units.items()):  # acceptor, offer (or the fully aggregated net)
                     if mode == "greedy":
@@ -224,13 +222,14 @@ class AggregatedTrainer(EpisodeLogging):
                     else:
                         u.group.wide_act(agg[k], action=numbers[i], generator=gen)
                 acc, off = env.decode_aggregated(numbers, self.fully, acceptor=acc_a, offer_core=off_a, n_bad=n_bad)
-            env.step(acc, off, obs=div_obs, rewards=rew, events=log.events)
+            env.step(acc, off, obs=div_obs, rewards=rew, events=log.events[0])
             log.add_aggregated(t, rew["aggregated_acceptor"], rew["aggregated_offer"])
+
+        per_replica = evaluation.run_episodes(log, episodes, one_round)
         if int(n_bad.item()):
             raise ValueError("Illegal Argument: %d action numbers outside the action space (Agent.py:651-652)"
                              % int(n_bad.item()))
-        log.harvest(episodes * self.ep_len)
-        return evaluation_result(mode, seed, E, log.episodes)
+        return evaluation.evaluation_result(mode, seed, E, per_replica)
 
     def flags(self) -> int:
         return self.env.flags()

@@ -285,7 +285,7 @@ def load(tr, path: str) -> dict:
     if tr.metric_bufs is not None:
         for b, s in zip(tr.metric_bufs, state["metric_bufs"]):
             b.copy_(s)
-        tr.episode_log = _decode(state["episode_log"])
+        tr.episode_log[:] = _decode(state["episode_log"])  # in place: the trainer's EpisodeLog appends to this list
     tr._policy_version += 1   # the acting tables are rebuilt from the loaded policy_old
     tr._rings_pending = False  # the rings belong to no rollout of this state
     tr._offers_pending = False

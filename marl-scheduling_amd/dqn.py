@@ -20,10 +20,12 @@ from dataclasses import dataclass
 import torch
 import torch.nn as nn
 
-from . import abi
+from . import abi, evaluation
 from ._lib import check, lib, ptr, stream_ptr
-from .episode_log import EpisodeLog, EpisodeLogging, check_evaluate_args, evaluation_result
+from .env import BatchedEnv
+from .episode_log import EpisodeLogging
 from .ppo import HipAdam
+from .trainer import allreduce_mean_grads, env_seed
 
 HIDDEN = 16  # DQNEntity (DQNmodules.py:41-46)
 KEYS = ("w1", "b1", "w2", "b2")
@@ -214,8 +216,6 @@ class DQNTrainer(EpisodeLogging):
     def __init__(self, cfg: abi.MsConfig, n_envs: int, hyper: DQNHyper | None = None, seed: int = 0, device=None,
                  episode_length: int | None = None, rank: int = 0, world_size: int = 1, process_group=None,
                  metrics: bool = False):
-        from .env import BatchedEnv
-        from .trainer import allreduce_mean_grads, env_seed
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         torch.cuda.set_device(self.device)
         if cfg.free_prices:
@@ -332,8 +332,7 @@ class DQNTrainer(EpisodeLogging):
     def eval_seed(self, n_envs: int | None = None) -> int:
         """Default base seed of evaluate()'s replicas: the training env's base seed of this rank plus 500_001
         (as Trainer.eval_seed), so the evaluation replicas meet no training replica's job stream."""
-        from .trainer import env_seed
-        return env_seed(self.seed, self.rank, int(n_envs or self.E)) + 500_001
+        return evaluation.eval_seed(self.seed, self.rank, int(n_envs or self.E))
 
     @torch.no_grad()
     def evaluate(self, episodes: int = 1, n_envs: int | None = None, mode: str = "greedy",
@@ -347,12 +346,8 @@ class DQNTrainer(EpisodeLogging):
         decides anything, and the Philox offset is a stateless argument); mode "hardcoded": the in-kernel
         rule-based agents, the baseline on the same job streams.
         Returns Trainer.evaluate's dict(mode, seed, n_envs, episodes, per_replica) of the divided values."""
-        from .env import BatchedEnv
-        episodes, E = check_evaluate_args(episodes, n_envs, self.E, mode, ("greedy", "hardcoded"))
-        seed = self.eval_seed(E) if seed is None else int(seed)
-        dev, N, C, L = self.device, self.N, self.C, self.L
-        env = BatchedEnv(self.cfg, E, seed=seed, device=dev)
-        log = EpisodeLog(env, slots=episodes)
+        episodes, seed, env, log = evaluation.fresh_env(self, episodes, n_envs, mode, ("greedy", "hardcoded"), seed)
+        dev, E, N, C, L = self.device, env.E, self.N, self.C, self.L
         s = env.shape
         obs = dict(acceptor=torch.zeros((E, N, C, s.acc_obs_stride), dtype=torch.int8, device=dev),
                    offer=torch.zeros((E, N, L, s.off_obs_stride), dtype=torch.int8, device=dev))
@@ -360,15 +355,16 @@ class DQNTrainer(EpisodeLogging):
         rew = env.reward_buffers()
         i8 = lambda u: torch.zeros((E, u), dtype=torch.int8, device=dev)
         act_acc, act_off, g_acc, g_off = i8(N * C), i8(N * L), i8(N * C), i8(N * L)
-        for _ in range(episodes * self.ep_len):
+
+        def one_round(t):
             if mode == "hardcoded":
-                env.step(None, None, obs=obs, rewards=rew, events=log.events)
-                continue
+                env.step(None, None, obs=obs, rewards=rew, events=log.events[0])
+                return
             self.off.policy.act(obs["offer"].view(E, N * L, -1), 1, 0.0, action=act_off, greedy=g_off)
             self.acc.policy.act(obs["acceptor"].view(E, N * C, -1), 1, 0.0, action=act_acc, greedy=g_acc)
-            env.step(g_acc.view(E, N, C), g_off.view(E, N, L), obs=obs, rewards=rew, events=log.events)
-        log.harvest(episodes * self.ep_len)
-        return evaluation_result(mode, seed, E, log.episodes)
+            env.step(g_acc.view(E, N, C), g_off.view(E, N, L), obs=obs, rewards=rew, events=log.events[0])
+
+        return evaluation.evaluation_result(mode, seed, E, evaluation.run_episodes(log, episodes, one_round))
 
     def flags(self) -> int:
         return self.env.flags()

@@ -29,11 +29,13 @@ from dataclasses import dataclass, field
 import numpy as np
 import torch
 
-from . import abi
+from . import abi, evaluation
 from ._lib import ABI_LOADED, capturing, has, hip_capture, ptr
 from .env import BatchedEnv
-from .ppo import (ActFrag, PPOGroup, PriceTable, act_round_free, act_round_greedy, combine_losses, discounted_returns,
-                  offer_act_free, offer_compress, offer_expand, reference_init_order, reference_nets, unit_returns)
+from .episode_log import EpisodeLogging
+from .evaluation import env_seed  # (its home; dqn.py, aggregated.py and the tests take it from here too)
+from .ppo import (ActFrag, PPOGroup, PriceTable, act_round_free, combine_losses, discounted_returns, offer_act_free,
+                  offer_compress, offer_expand, reference_init_order, reference_nets, unit_returns)
 
 
 @dataclass
@@ -104,12 +106,6 @@ class _Unit:
         return x, a, lp, ret
 
 
-def env_seed(seed: int, rank: int, n_envs: int) -> int:
-    """Base seed of a rank's replicas: replica e of rank r is random.seed(base + e), so the ranks'
-    job streams are disjoint for seeds up to 1000003 / world_size apart."""
-    return seed * 1_000_003 + rank * n_envs
-
-
 def allreduce_mean_grads(params, world_size: int, group=None):
     """Average the gradients over ranks with one flattened all-reduce (RCCL over xGMI on GPUs,
     gloo on CPU). Shards are equal, so the mean of the per-rank mean losses' gradients is the
@@ -157,7 +153,7 @@ class EnvParts:
         return f
 
 
-class Trainer:
+class Trainer(EpisodeLogging):
     def __init__(self, cfg: abi.MsConfig, n_envs: int, arch: str = "local", hyper: Hyper | None = None, seed: int = 0,
                  device=None, rank: int = 0, world_size: int = 1, process_group=None, fused: bool = True,
                  use_graph: bool = True, common_rows: bool = True, rollout_streams: int = 1, metrics: bool = False,
@@ -199,11 +195,7 @@ class Trainer:
         if hardcoded_agents is not None:  # evaluate()'s checks, and somebody must be left to train
             if self.free:
                 raise ValueError("the hard-coded agents act under fixed prices only")
-            given = list(hardcoded_agents)
-            if any(isinstance(a, bool) or not isinstance(a, (int, np.integer, float, np.floating)) or a != int(a)
-                   for a in given) or any(not 0 <= int(a) < N for a in given):
-                raise ValueError("hardcoded_agents must be agent indices in [0, %d)" % N)
-            self.hardcoded = sorted({int(a) for a in given})
+            self.hardcoded = evaluation.agent_indices(hardcoded_agents, N)
             if len(self.hardcoded) == N:
                 raise ValueError("hardcoded_agents covers every agent: nothing would train")
             if self.hardcoded and arch != "global" and not fused:
@@ -318,11 +310,13 @@ class Trainer:
             env.reset(dict(self._acc_out(0, e0, e1), offer=self._off_obs[0][e0:e1]))
         # episode metrics (trainPPO.py:153-226): the env kernel adds every round into per-replica
         # accumulators, slot (round // episodeLength) % slots; finished episodes are read after each
-        # rollout (metrics.py) and their slots zeroed before reuse
+        # rollout (episode_log.py) and their slots zeroed before reuse
         self.ep_len = int(self.cfg.episode_length)
         self.metric_slots = -(-T // self.ep_len) + 1
-        self.metric_bufs = [env.metrics_buffer(self.metric_slots) for env, _, _ in self.env.parts] if metrics else None
-        self.episode_log = []
+        split = None if self.hardcoded is None else (lambda ep: evaluation.split_sides(ep, self.hardcoded))
+        self._init_episode_log(metrics, [env for env, _, _ in self.env.parts], slots=self.metric_slots, hook=split,
+                               episodeLength=self.ep_len, UPDATE_STEP=T, n_envs=self.E * world_size)
+        self.metric_bufs = self._elog.bufs if metrics else None  # one per part; the captured rollouts hold them
         # one rank: each unit type's update on its own stream (MS_UPDATE_STREAMS=0: one stream). Round 4: the
         # update 10.06 -> 9.63 ms but the next rollout 14.50 -> 15.63 ms (every rollout launch slower after a
         # multi-stream update graph), so it was off. Round 6, with cfg3's rollout one launch: update 8.50 -> 8.05 ms,
@@ -562,8 +556,8 @@ class Trainer:
                    agent=sl(self.agent_reward), auctioneer=sl(self.auct_reward),
                    price=sl(self.price.rewards[t]).view(E, N, L) if self.free else None)
         ev = dict(launch_span=self.spans[t // self.span_every, k]) if self.span_every and t % self.span_every == 0 else None
-        if self.metric_bufs is not None:
-            ev = dict(ev or {}, metrics=self.metric_bufs[k])
+        if self._elog is not None:
+            ev = dict(ev or {}, metrics=self._elog.bufs[k])
         nxt = self._fused_next(t + 1, k) if self.fused_step and t + 1 < self.T else None
         if self.hc_mask:  # a mixed market: the ring slot receives what the masked agents played
             acc_t, off_t = sl(self.acc.actions[t]).view(E, N, C), sl(self.off.actions[t]).view(E, N, L)
@@ -599,8 +593,8 @@ class Trainer:
         rew = dict(offer=sl(self.off.rewards[0]).view(E, N, L), acceptor=sl(self.acc.rewards[0]).view(E, N, C),
                    agent=sl(self.agent_reward), auctioneer=sl(self.auct_reward))
         ev = dict(launch_span=self.spans[0, k]) if self.span_every else None
-        if self.metric_bufs is not None:  # every round adds into the slot of its own episode (not strided)
-            ev = dict(ev or {}, metrics=self.metric_bufs[k])
+        if self._elog is not None:  # every round adds into the slot of its own episode (not strided)
+            ev = dict(ev or {}, metrics=self._elog.bufs[k])
         b = lambda x: x.stride(0) * x.element_size()  # bytes between ring slots t and t + 1
         strides = abi.MsRoundStrides(b(self.acc.actions), b(self.off.actions), b(self.acc_rows), b(self.acc_owner),
                                      b(self._off_obs), b(self.off.rewards), b(self.acc.rewards), 0, 0,
@@ -644,8 +638,8 @@ class Trainer:
                    agent=sl(self.agent_reward), auctioneer=sl(self.auct_reward),
                    price=sl(self.price.rewards[0]).view(E, N, L))
         ev = dict(launch_span=self.spans[0, k]) if self.span_every else None
-        if self.metric_bufs is not None:
-            ev = dict(ev or {}, metrics=self.metric_bufs[k])
+        if self._elog is not None:
+            ev = dict(ev or {}, metrics=self._elog.bufs[k])
         b = lambda x: x.stride(0) * x.element_size()  # bytes between ring slots t and t + 1
         strides = abi.MsRoundStridesFree(b(self.acc.actions), b(self.off.actions), b(self.acc_rows), b(self.acc_owner),
                                          b(self._off_obs), b(self.off.rewards), b(self.price.rewards),
@@ -1204,101 +1198,17 @@ class Trainer:
         self.iterations += 1
         if self.diagnostics:  # after the update's end event: the rollout and update spans do not see it
             self.diagnostics_log.append(self.update_diagnostics())
-        if self.metric_bufs is not None:
-            self._harvest_episodes()
+        if self._elog is not None:  # the episodes finished by now (trainPPO.py:200-226), into self.episode_log
+            self._elog.harvest(self.rounds_done)
         return losses
 
-    # ---- metrics
-    def _harvest_episodes(self):
-        """Per-replica values of every episode finished by now (trainPPO.py:200-226), appended to
-        self.episode_log; their accumulator slots are zeroed for reuse."""
-        from . import metrics as mx
-        s = self.env.shape
-        done = self.rounds_done // self.ep_len
-        while len(self.episode_log) < done:
-            slot = len(self.episode_log) % self.metric_slots
-            raw = torch.cat([b[slot] for b in self.metric_bufs]).cpu().numpy()
-            for b in self.metric_bufs:
-                b[slot].zero_()
-            ep = mx.episode_values(mx.view(raw), self.cfg, self.ep_len, s.n_agents, s.n_cores, s.collection_length)
-            if self.hardcoded is not None:  # what each side earns (evaluate()'s split), per replica
-                for d in ep:
-                    d["agentRew_hardcoded"], d["agentRew_learned"] = mx.split_agent_rew(d["agentRew"], self.hardcoded)
-            self.episode_log.append(ep)
-
-    # ---- evaluation
+    # ---- evaluation (evaluation.py)
     def eval_seed(self, n_envs: int | None = None) -> int:
         """Default base seed of evaluate()'s replicas: the training env's base seed of this rank (env_seed)
         plus 500_001, half the distance between two trainer seeds' ranges, so the evaluation replicas
         [base, base + n_envs) meet no training replica's job stream while world_size * E < 500_001."""
-        return env_seed(self.seed, self.rank, int(n_envs or self.E)) + 500_001
+        return evaluation.eval_seed(self.seed, self.rank, int(n_envs or self.E))
 
-    def _eval_buffers(self, E: int):
-        """evaluate()'s observation / action / reward tensors for E replicas (kept between calls)."""
-        cache = self.__dict__.setdefault("_eval_cache", {})
-        if E not in cache:
-            s, dev, i8 = self.env.shape, self.device, torch.int8
-            N, C, L = self.N, self.C, self.L
-            z = lambda *shape, dtype=i8: torch.zeros(shape, dtype=dtype, device=dev)
-            b = dict(offer=z(E, N * L, s.off_obs_stride), acc_action=z(E, N * C), off_action=z(E, N * L),
-                     acc_logprob=z(E, N * C, dtype=torch.float32), off_logprob=z(E, N * L, dtype=torch.float32))
-            if self.compact:
-                b.update(core_rows=z(E, C, s.acc_obs_stride), core_owner=z(E, C))
-            else:
-                b.update(acceptor=z(E, N * C, s.acc_obs_stride))
-            if self.free:
-                b.update(price_state=z(E, N * L, 4), price_action=z(E, N * L), env_price=z(E, N * L),
-                         price_logprob=z(E, N * L, dtype=torch.float32))
-            b["rewards"] = dict(offer=z(E, N, L, dtype=torch.float32), acceptor=z(E, N, C, dtype=torch.int32),
-                                agent=z(E, N, dtype=torch.int32), auctioneer=z(E, C, dtype=torch.int32),
-                                price=z(E, N, L, dtype=torch.float32) if self.free else None)
-            cache[E] = b
-        return cache[E]
-
-    def _eval_act(self, b: dict, mode: str, t: int, philox_seed: int):
-        """getActionForAllAgents of evaluation round t on the observations in b, with policy_old (the nets the
-        next rollout acts with): greedy (argmax) or sampled picks, into b's action tensors."""
-        N, C, L = self.N, self.C, self.L
-        off, acc = self.off.group.policy_old, self.acc.group.policy_old
-        price = self.price.group.policy_old if self.free else None
-        if mode == "greedy":
-            if self.compact:
-                out = dict(core_action=b["off_action"])
-                if self.free:
-                    out.update(price_state=b["price_state"], price_action=b["price_action"], env_price=b["env_price"])
-                act_round_greedy(off, price, b["offer"], acc, b["core_rows"], b["core_owner"], self.acc_common, C,
-                                 out, b["acc_action"])
-                return
-            off.act_greedy(b["offer"], N * L, action=b["off_action"], logprob=b["off_logprob"])
-            if self.free:
-                # FreePriceOfferPPO.selectAction (PPOmodules.py:312-332) on the greedy core action a:
-                # [obs[2a], obs[2a+1], obs[2C], obs[2C+1]], or the dummy [-5, -5, -5, -5] when a == 0
-                a = b["off_action"].long()
-                idx = torch.stack([2 * a, 2 * a + 1, torch.full_like(a, 2 * C), torch.full_like(a, 2 * C + 1)], -1)
-                st = torch.gather(b["offer"], 2, idx)
-                b["price_state"].copy_(torch.where((a == 0).unsqueeze(-1), torch.full_like(st, -5), st))
-                price.act_greedy(b["price_state"], N * L, action=b["price_action"], logprob=b["price_logprob"])
-                b["env_price"].copy_(torch.where(a == 0, torch.full_like(b["price_action"], -5), b["price_action"]))
-            acc.act_greedy(b["acceptor"], N * C, action=b["acc_action"], logprob=b["acc_logprob"])
-            return
-        # sampled picks: the training calls with the rounds' static Philox offsets (_act_part), no device counter
-        base = 8 * t
-        out = dict(core_action=b["off_action"], core_logprob=b["off_logprob"])
-        if self.free:
-            out.update(price_state=b["price_state"], price_action=b["price_action"],
-                       price_logprob=b["price_logprob"], env_price=b["env_price"])
-        if self.compact:
-            act_round_free(off, price, b["offer"], acc, b["core_rows"], b["core_owner"], self.acc_common, C,
-                           philox_seed, base + 1, base + 3, out, b["acc_action"], b["acc_logprob"])
-            return
-        if self.free:
-            offer_act_free(off, price, b["offer"], C, philox_seed, base + 1, out)
-        else:
-            off.act(b["offer"], N * L, philox_seed, base + 1, action=b["off_action"], logprob=b["off_logprob"])
-        acc.act(b["acceptor"], N * C, philox_seed, base + 3, action=b["acc_action"], logprob=b["acc_logprob"],
-                common_row=self.acc_common if self.common_rows else None)
-
-    @torch.no_grad()
     def evaluate(self, episodes: int = 1, n_envs: int | None = None, mode: str = "greedy", seed: int | None = None,
                  trace: bool = False, hardcoded_agents=None) -> dict:
         """Evaluate the current policy (policy_old, the nets the next rollout acts with) for `episodes` episodes
@@ -1330,69 +1240,7 @@ class Trainer:
         Returns dict(mode, seed, n_envs, episodes=[metrics.reduce_replicas(ep), ...] (the argsDict values
         Plot.py reads, averaged over replicas), per_replica=[[dict per replica] per episode]); with trace also
         trace=[per round: the observations acted on and every action array fed to the env, CPU tensors]."""
-        from . import metrics as mx
-        if mode not in ("greedy", "sample", "hardcoded"):
-            raise ValueError("mode must be 'greedy', 'sample' or 'hardcoded'")
-        if mode == "hardcoded" and self.free:
-            raise ValueError("the hard-coded agents act under fixed prices only")
-        episodes, E = int(episodes), int(n_envs or self.E)
-        if episodes < 1 or E < 1:
-            raise ValueError("episodes and n_envs must be >= 1")
-        mixed = hardcoded_agents is not None
-        if mixed:
-            if mode == "hardcoded":
-                raise ValueError("hardcoded_agents selects agents of a learned population: mode 'greedy' or 'sample'")
-            if self.free:
-                raise ValueError("the hard-coded agents act under fixed prices only")
-            given = list(hardcoded_agents)
-            hc = sorted({int(a) for a in given})
-            if any(a != int(a) for a in given) or any(not 0 <= a < self.N for a in hc):
-                raise ValueError("hardcoded_agents must be agent indices in [0, %d)" % self.N)
-        seed = self.eval_seed(E) if seed is None else int(seed)
-        N, C, L = self.N, self.C, self.L
-        b = self._eval_buffers(E)
-        env = self.eval_env = BatchedEnv(self.cfg, E, seed=seed, device=self.device)
-        obs_keys = ("core_rows", "core_owner", "offer") if self.compact else ("acceptor", "offer")
-        obs = {k: b[k] for k in obs_keys}
-        env.reset(obs)
-        mbuf = env.metrics_buffer(episodes)  # round r adds into slot (r // episode_length) % episodes
-        philox_seed = (seed * 7919) & 0xFFFFFFFFFFFFFFFF
-        rounds = []
-        if mixed:  # the actions the rounds used (the rules' picks in the given agents' rows)
-            taken = dict(acceptor=torch.empty_like(b["acc_action"]), offer_core=torch.empty_like(b["off_action"]))
-        for t in range(episodes * self.ep_len):
-            if mode == "hardcoded":
-                acts = (None, None, None)
-            else:
-                self._eval_act(b, mode, t, philox_seed)
-                acts = (b["acc_action"].view(E, N, C), b["off_action"].view(E, N, L),
-                        b["env_price"].view(E, N, L) if self.free else None)
-            if trace:
-                rec = {k: b[k].cpu() for k in obs_keys}
-                if mode != "hardcoded":
-                    rec.update(acceptor_action=b["acc_action"].cpu(), offer_action=b["off_action"].cpu())
-                    if self.free:
-                        rec.update(price_state=b["price_state"].cpu(), price_action=b["price_action"].cpu(),
-                                   offer_price=b["env_price"].cpu())
-                rounds.append(rec)
-            if mixed:
-                env.step_mixed(acts[0], acts[1], hc, obs=obs, rewards=b["rewards"], events=dict(metrics=mbuf),
-                               taken=taken)
-                if trace:
-                    rec.update(acceptor_action=taken["acceptor"].cpu(), offer_action=taken["offer_core"].cpu())
-                continue
-            env.step(*acts, obs=obs, rewards=b["rewards"], events=dict(metrics=mbuf))
-        raw = mbuf.cpu().numpy()
-        per_replica = [mx.episode_values(mx.view(raw[k]), self.cfg, self.ep_len, N, C, L) for k in range(episodes)]
-        res = dict(mode=mode, seed=seed, n_envs=E, episodes=[mx.reduce_replicas(ep) for ep in per_replica],
-                   per_replica=per_replica)
-        if mixed:
-            res["hardcoded_agents"] = hc
-            for ep in res["episodes"]:
-                ep["agentRew_hardcoded"], ep["agentRew_learned"] = mx.split_agent_rew(ep["agentRew"], hc)
-        if trace:
-            res["trace"] = rounds
-        return res
+        return evaluation.evaluate(self, episodes, n_envs, mode, seed, trace, hardcoded_agents)
 
     # ---- checkpoints (checkpoint.py)
     def save_checkpoint(self, path: str) -> dict:
@@ -1416,21 +1264,6 @@ class Trainer:
         trainer's shape terms, arch and price mode: evaluate() then runs the saved policy."""
         from . import checkpoint
         return checkpoint.load_policy(self, path)
-
-    def args_dict(self, replica="mean", params=None):
-        """argsDict of the finished episodes (trainPPO.py:229-243): replica = "mean" averages the
-        replicas' values per episode, an int picks one replica."""
-        from . import metrics as mx
-        p = dict(params or {})
-        p.setdefault("episodeLength", self.ep_len)
-        p.setdefault("UPDATE_STEP", self.T)
-        p.setdefault("n_envs", self.E * self.world_size)
-        return mx.args_dict(self.episode_log, self.cfg, p, replica=replica)
-
-    def save_args_dict(self, directory: str = ".", file_name: str = "data{}.pkl", replica="mean", params=None):
-        """args_dict() pickled as the first free data{i}.pkl in directory (trainPPO.py:245-251)."""
-        from . import metrics as mx
-        return mx.save_args_dict(self.args_dict(replica, params), file_name, directory)
 
     @property
     def timings(self):

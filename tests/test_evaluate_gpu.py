@@ -189,6 +189,22 @@ def test_hardcoded_baseline(ms):
         t.evaluate(mode="best")
 
 
+def test_n_envs_below_one_is_refused(ms):
+    """n_envs must be >= 1 (None alone means E): a refused call leaves the training env and the rings alone."""
+    t = _trainer("cfg2")
+    losses = [t.iteration()]
+    before = _training_state(t, losses)
+    with pytest.raises(ValueError):
+        t.evaluate(n_envs=0)
+    with pytest.raises(ValueError):
+        t.evaluate(n_envs=-2, mode="hardcoded")
+    after = _training_state(t, losses)
+    assert after.keys() == before.keys() and after["env_round"] == T
+    for k in before:
+        assert _same(after[k], before[k]), k
+    assert _same(t.evaluate(n_envs=None), t.evaluate(n_envs=E))
+
+
 @pytest.mark.parametrize("name", ["cfg1", "cfg2", "cfg3"])
 def test_sample_mode_reproducible(ms, name):
     t = _trainer(name)

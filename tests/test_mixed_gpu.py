@@ -316,6 +316,8 @@ def test_evaluate_mixed_refusals(ms):
         t.evaluate(mode="greedy", hardcoded_agents=[t.N])
     with pytest.raises(ValueError):
         t.evaluate(mode="greedy", hardcoded_agents=[-1])
+    with pytest.raises(ValueError):  # (a bool is no agent index, as in Trainer(hardcoded_agents=...))
+        t.evaluate(mode="greedy", hardcoded_agents=[True])
     with pytest.raises(ValueError):
         ev._trainer("cfg3").evaluate(mode="greedy", hardcoded_agents=[0])
 

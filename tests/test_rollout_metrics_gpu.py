@@ -87,7 +87,7 @@ def _compare(ms, trs, iters=2):
                 assert bool(same.all()), (it, i, k, int((~same).sum()), same.numel())
         losses = [t.update() for t in trs]
         for t in trs:
-            t._harvest_episodes()
+            t._elog.harvest(t.rounds_done)
         for i in range(1, len(trs)):
             for k in losses[0]:
                 assert torch.equal(losses[0][k], losses[i][k]), (it, i, k)
