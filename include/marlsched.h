@@ -737,9 +737,13 @@ int ms_unit_returns(const void* rewards, int32_t rewards_i32, int32_t T, int64_t
  *   mean_r[-min(ratio*adv, clamp(ratio, 1-eps, 1+eps)*adv)] + 0.5*mean_r[(V-G)^2] - 0.01*mean_r[entropy]
  * over the R = T*E transitions of sub-unit unit_of_group[g], read straight from the
  * int8 rollout buffer (row r = t*E + e). Gradients are written (not accumulated) in
- * torch .grad layouts; the optimizer step stays with the caller. Deterministic. */
+ * torch .grad layouts; the optimizer step stays with the caller. Deterministic.
+ * Shapes: in_dim in [1, 255], n_actions in [1, 128], hidden 16, stride >= in_dim and a multiple of 4; MS_EINVAL
+ * otherwise, before any launch. */
 typedef struct ms_ppo_batch {
-    const int8_t* states;          /* [R][U][stride] observation rows */
+    /* [R][U][stride] observation rows. Bytes in_dim .. stride - 1 of a row do not reach the gradient, whatever
+     * they hold (a row whose pad bytes differ from common_row's is not equal to it and runs on its own) */
+    const int8_t* states;
     const int8_t* actions;         /* [R][U] */
     const float* old_logprobs;     /* [R][U] */
     const float* returns;          /* [T][E][G] normalised (ms_unit_returns output) */

@@ -1196,8 +1196,9 @@ static int ppo_grad(const ms_mlp_params* a, const ms_mlp_params* c, const ms_ppo
     if (a->hidden != 16 || c->hidden != 16) return fail(MS_EINVAL, "hidden width must be 16");
     if (c->n_actions != 1 || c->in_dim != a->in_dim || c->n_groups != a->n_groups)
         return fail(MS_EINVAL, "critic must be [D -> 16 -> 16 -> 1] with the actor's groups");
-    if (a->in_dim < 1 || a->in_dim > 256 || a->n_actions < 1 || a->n_actions > 128)
-        return fail(MS_EINVAL, "in_dim must be in [1, 256] and n_actions in [1, 128]");
+    // (in_dim 256 has no kernel: the staged input tile keeps one column past the inputs for the bias gradient)
+    if (a->in_dim < 1 || a->in_dim > 255 || a->n_actions < 1 || a->n_actions > 128)
+        return fail(MS_EINVAL, "in_dim must be in [1, 255] and n_actions in [1, 128]");
     if (b->stride < a->in_dim || (b->stride & 3) || b->T < 1 || b->E < 1 || b->U < 1)
         return fail(MS_EINVAL, "bad batch shape");
     if ((!b->states && !tmpl) || !b->actions || !b->old_logprobs || !b->returns || !b->unit_of_group)

@@ -254,6 +254,7 @@ __global__ void __launch_bounds__((64 * GradLds<NQ, NT, MODEX>::WPB), ((NQ * NT 
     // input byte D of every staged row reads 1 (the bias column of dW1)
     const int one_dw = D >> 2;
     const uint32_t one_bit = 1u << (8 * (D & 3));
+    const uint32_t one_keep = ~(0xffu << (8 * (D & 3)));
     // compact acceptor rows: unit u = agent u / C, core u % C reads core row (r, u % C)
     constexpr bool OWNROWS = MODE == kOwnerRow || MODE == kMaskRow;  // rows are compact core rows
     const int own_c = OWNROWS ? u % p.owner_C : 0;
@@ -425,7 +426,7 @@ __global__ void __launch_bounds__((64 * GradLds<NQ, NT, MODEX>::WPB), ((NQ * NT 
             for (int h = 0; h < 2; h++) {
                 const int cc = 8 * s + 2 * g4 + h;
                 const uint32_t w = cc < stride4 ? xr[s][h] : 0u;  // bytes past the row read 0
-                xw[s][h] = cc == one_dw ? (w | one_bit) : w;
+                xw[s][h] = cc == one_dw ? ((w & one_keep) | one_bit) : w;  // (whatever the row's pad byte D held)
                 if (cc < 4 * NQ) sX[(16 * half + j) * XPD + cc] = xw[s][h];
             }
         Fwd f;
