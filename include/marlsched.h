@@ -862,7 +862,11 @@ typedef struct ms_wide_batch {
 
 /* One K-epoch gradient of PPO.update for the wide nets: grads = d/dθ of each group's
  * mean_r[-min(surr)] + 0.5 mean_r[(V-G)^2] - 0.01 mean_r[entropy] (same outputs as ms_ppo_grad;
- * the tensors are overwritten). Deterministic (fixed-order sums). */
+ * the tensors are overwritten). Deterministic (fixed-order sums).
+ * Both take hidden 32 or 64, in_dim in [1, 255], n_actions in [1, 2^24], n_groups >= 1 (ms_wide_grad at most
+ * 65535) and rows >= 1. ms_wide_workspace_bytes returns 0 for anything outside these ranges and for a workspace
+ * past 64 GiB (ms_last_error says which); ms_wide_grad refuses the same shapes, and a workspace smaller than that
+ * size, with MS_EINVAL before any launch. */
 size_t ms_wide_workspace_bytes(const ms_mlp_params* actor, int64_t rows);
 int ms_wide_grad(const ms_mlp_params* actor, const ms_mlp_params* critic, const ms_wide_batch* batch, float eps_clip,
                  void* workspace, size_t workspace_bytes, const ms_ppo_grads* grads, void* stream);

@@ -1921,6 +1921,11 @@ size_t ms_wide_workspace_bytes(const ms_mlp_params* a, int64_t rows) {
     if (!a || rows < 1 || a->n_groups < 1 || a->n_actions < 1 || a->in_dim < 1 ||
         (a->hidden != 32 && a->hidden != 64))
         return 0;
+    // the ranges ms_wide_grad accepts (wide_check): no size for a net it refuses
+    if (a->in_dim > 255 || a->n_actions > (1 << 24)) {
+        fail(MS_EINVAL, "ms_wide_workspace_bytes: in_dim must be in [1, 255], n_actions in [1, 2^24], n_groups >= 1");
+        return 0;
+    }
     const size_t b = wide_plan(a, rows).bytes;
     if (b > kWideWorkspaceCap) {
         fail(MS_EINVAL, "ms_wide_workspace_bytes: %zu bytes for %d actions exceeds the 64 GiB bound", b, a->n_actions);
