@@ -74,8 +74,7 @@ def layer1_compact_reference(w1, b1, core_rows, core_owner, n_agents: int, d_acc
     row F elsewhere (Agent.py:167-212), so W1 x_a + b1 = (b1 + sum_c W1_c F) + sum_{c owned by a}
     W1_c (R_c - F). core_rows [E, C, stride] int8, core_owner [E, C] -> [E * N, 128]."""
     E, C, _ = core_rows.shape
-    O = (d_acc - 3) // 2
-    foreign = torch.tensor([0.0, -1.0, -1.0] + [-2.0] * (2 * O), device=core_rows.device)
+    foreign = torch.tensor([0.0, -1.0, -1.0] + [-2.0] * (d_acc - 3), device=core_rows.device)  # d_acc = 3 + 2 O
     w1c = w1.view(w1.shape[0], C, d_acc)
     base = b1 + torch.einsum("jcd,d->j", w1c, foreign)
     dc = core_rows[:, :, :d_acc].float() - foreign

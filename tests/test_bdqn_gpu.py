@@ -189,8 +189,9 @@ def test_act_kernel_is_the_argmax_of_q(ms, role):
 
 @pytest.mark.parametrize("n", [17, 33, 50, 65, 100])
 def test_act_kernel_masks_padded_action_tiles(ms, n):
-    """Branch widths whose tile count is not an instantiated NMT (n = 17: NMT 3 for 2 tiles; 50, 65,
-    100: NMT 7 for 4..6 tiles; 33 is exact) on int8 rows (layer 1 in the kernel): the zero-padded
+    """Branch widths that are no multiple of the 16-action tile (launch_bdqn_act instantiates NMT =
+    ceil(n / 16) exactly: n = 17, 33, 50, 65, 100 run NMT 2, 3, 4, 5, 7, each with a partly filled
+    last tile) on int8 rows (layer 1 in the kernel): the zero-padded
     rows past n join neither the mean nor the argmax, so every action is < n and the greedy ones are
     the first argmax of the fp32 reference's q (BranchingDQNModules.py:88-101). The advantage biases
     are shifted so the mean advantage is negative, where a padded row would win."""
