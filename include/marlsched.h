@@ -22,6 +22,7 @@
  *   ms_wide_act_greedy <- the same for the aggregated agents' nets (ms_wide_act's forward)
  *   ms_policy_evaluate <- ActorCritic.evaluate             PPOmodules.py:65-72
  *   ms_action_hist  <- the action logging of trainPPOExperiment3.py:215-237, as histograms per unit
+ *   ms_action_table <- the same rings as joint histograms, action by job priority (no counterpart)
  *   ms_discounted_returns, ms_unit_returns <- PPO.update return estimate  PPOmodules.py:128-137
  *
  * Conventions: plain pointers and sizes; every device pointer is a HIP device
@@ -524,6 +525,43 @@ typedef struct ms_action_hist_args {
     int64_t* bad;       /* or NULL */
 } ms_action_hist_args;
 int ms_action_hist(const ms_action_hist_args* args, void* stream);
+
+/* Action-by-key tables (detect with dlsym: MS_ABI_VERSION is unchanged): counts += how often each action was taken
+ * under each value of a key byte that the rings hold beside it, per episode and per bin of units: which core, or
+ * which price, for a job of which priority (the free-price experiments' question, which a histogram pooled over all
+ * jobs cannot answer). Integer counts: exact, and the same from run to run.
+ *   rows    r = t * n_envs + e for t < n_rounds; row r lands in slot ((round0 + t) / episode_length) % n_slots (the
+ *           histogram's rule)
+ *   counts  int64 [n_slots][n_bins][n_keys][n_actions], n_bins = n_units / units_per_bin, added into and never zeroed
+ *   actions element (r, u) at actions[r * row_stride + u * unit_stride] (bytes); keys at keys[r * key_row_stride +
+ *           u * key_unit_stride]: [T][E][U] rings, unit-major [U][T][E] rings, byte 2 of a [..][U][4] price state
+ *           (unit stride 4), the pair bytes of compact offers (unit stride 2) and byte 2C of the offer rows (unit
+ *           stride = a unit's row) are all read in place
+ * For element (r, u): k = keys[r][u] - key_min. k outside [0, n_keys): the element is skipped, its action byte is not
+ * examined, and *skipped (int64 on the device, optional) += 1. Otherwise an action outside [0, n_actions) adds one
+ * to *bad (optional) and nothing is binned. Otherwise counts[slot][u / units_per_bin][k][action] += 1. No byte forms
+ * an index before it has been range-checked. units_per_bin 1: a table per unit; L: per agent; n_units: one table.
+ * MS_EINVAL with a message, nothing launched and counts untouched: n_actions or n_keys outside [1, 64], n_bins *
+ * n_keys * n_actions above 16383 (the counters a workgroup keeps), units_per_bin < 1 or not a divisor of n_units,
+ * key_min outside [-128, 127], n_units, n_envs, n_rounds, episode_length, n_slots or a stride < 1, round0 < 0,
+ * actions, keys or counts NULL, more rows than one launch counts in 32 bits. The arrays must hold n_rounds * n_envs
+ * rows at their strides (the kernel does not see their sizes). */
+typedef struct ms_action_table_args {
+    const int8_t* actions;
+    int64_t row_stride, unit_stride;
+    const int8_t* keys;
+    int64_t key_row_stride, key_unit_stride;
+    int32_t n_units, units_per_bin;
+    int32_t n_keys, key_min;
+    int32_t n_actions, reserved;
+    int64_t n_envs;
+    int64_t round0;     /* the first row's round */
+    int32_t n_rounds, episode_length, n_slots, reserved2;
+    int64_t* counts;
+    int64_t* skipped;   /* or NULL */
+    int64_t* bad;       /* or NULL */
+} ms_action_table_args;
+int ms_action_table(const ms_action_table_args* args, void* stream);
 
 /* One round's getActionForAllAgents (SchedulingEnvironment.py:150-172), greedy, in one launch (two for shapes
  * without a paired kernel), on the observations ms_env_step emits: offer rows + compact acceptor rows

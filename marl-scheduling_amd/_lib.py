@@ -140,11 +140,12 @@ def _load():
                                     ct.POINTER(abi.MsPpoGrads), P]),
     }
     # entry points added without an ABI step (compact offer observations; ms_policy_evaluate, whose users are
-    # GroupedActorCritic.evaluate_hip and the update diagnostics; ms_action_hist, the action log's; ms_wide_act_greedy,
+    # GroupedActorCritic.evaluate_hip and the update diagnostics; ms_action_hist and ms_action_table, the action log's; ms_wide_act_greedy,
     # the aggregated nets' argmax acting for AggregatedTrainer.evaluate): a library of
     # this ABI built before them loads without them, and their users ask has()
     optional = {
         "ms_action_hist": (ct.c_int, [ct.POINTER(abi.MsActionHistArgs), P]),
+        "ms_action_table": (ct.c_int, [ct.POINTER(abi.MsActionTableArgs), P]),
         "ms_wide_act_greedy": (ct.c_int, [ct.POINTER(abi.MsMlpParams), P, i32, i64, P, P, P]),
         "ms_policy_evaluate": (ct.c_int, [ct.POINTER(abi.MsMlpParams), ct.POINTER(abi.MsMlpParams), P, i32, i64, i32, i32,
                                           P, P, P, P, P]),
@@ -220,7 +221,7 @@ EXPORTED = (
     "ms_bdqn_act", "ms_bdqn_act_compact", "ms_bdqn_update_workspace_bytes", "ms_bdqn_update", "ms_wide_act", "ms_wide_workspace_bytes",
     "ms_wide_grad",
     "ms_env_rollout_act_free_compact", "ms_offer_compress", "ms_offer_expand", "ms_ppo_grad_offer_compact",
-    "ms_action_hist", "ms_wide_act_greedy",
+    "ms_action_hist", "ms_wide_act_greedy", "ms_action_table",
 )
 
 

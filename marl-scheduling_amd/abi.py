@@ -252,6 +252,15 @@ class MsActionHistArgs(ct.Structure):  # ms_action_hist_args
                 ("reserved", ct.c_int32), ("counts", ct.c_void_p), ("bad", ct.c_void_p)]
 
 
+class MsActionTableArgs(ct.Structure):  # ms_action_table_args
+    _fields_ = [("actions", ct.c_void_p), ("row_stride", ct.c_int64), ("unit_stride", ct.c_int64),
+                ("keys", ct.c_void_p), ("key_row_stride", ct.c_int64), ("key_unit_stride", ct.c_int64),
+                ("n_units", ct.c_int32), ("units_per_bin", ct.c_int32), ("n_keys", ct.c_int32), ("key_min", ct.c_int32),
+                ("n_actions", ct.c_int32), ("reserved", ct.c_int32), ("n_envs", ct.c_int64), ("round0", ct.c_int64),
+                ("n_rounds", ct.c_int32), ("episode_length", ct.c_int32), ("n_slots", ct.c_int32),
+                ("reserved2", ct.c_int32), ("counts", ct.c_void_p), ("skipped", ct.c_void_p), ("bad", ct.c_void_p)]
+
+
 class MsQnetParams(ct.Structure):
     _fields_ = [("w1", ct.c_void_p), ("b1", ct.c_void_p), ("w2", ct.c_void_p), ("b2", ct.c_void_p),
                 ("in_dim", ct.c_int32), ("hidden", ct.c_int32), ("n_actions", ct.c_int32), ("n_groups", ct.c_int32)]

@@ -17,11 +17,11 @@ HEADERS=("${HERE}"/csrc/*.h "${HERE}/../include/marlsched.h")  # every header: o
 CCVER="$("${HIPCC}" --version 2>/dev/null | head -3 | tr '\n' ' ')"
 objs=()
 pids=()
-for src in env_kernels.hip acc_fill_kernels.hip policy_kernels.hip act_pair_kernels.hip greedy_kernels.hip evaluate_kernels.hip action_hist_kernels.hip returns_kernels.hip ppo_kernels.hip agg_kernels.hip dqn_kernels.hip bdqn_kernels.hip bdqn_update_kernels.hip wide_kernels.hip snapshot_kernels.hip capi.cpp; do
+for src in env_kernels.hip acc_fill_kernels.hip policy_kernels.hip act_pair_kernels.hip greedy_kernels.hip evaluate_kernels.hip action_hist_kernels.hip action_table_kernels.hip returns_kernels.hip ppo_kernels.hip agg_kernels.hip dqn_kernels.hip bdqn_kernels.hip bdqn_update_kernels.hip wide_kernels.hip snapshot_kernels.hip capi.cpp; do
   obj="${OBJDIR}/${src%.*}.o"
   # the env round reproduces Python's float64 arithmetic: no contraction there; the policy
   # and PPO kernels follow torch's f32 (which fuses freely) within tolerance: fma allowed
-  # (the action histogram counts in integers only and keeps the default)
+  # (the action histogram and the action table count in integers only and keep the default)
   contract=(-ffp-contract=off)
   [[ "${src}" == policy_kernels.hip || "${src}" == act_pair_kernels.hip || "${src}" == greedy_kernels.hip || "${src}" == returns_kernels.hip ]] && contract=(-ffp-contract=fast)
   # the gradient kernel's variants (common rows by bytes or by owners) must agree bit for bit: fma only

@@ -92,10 +92,11 @@ def config_of(t: torch.Tensor) -> abi.MsConfig:
 def make_manifest(cfg: abi.MsConfig, arch: str, E: int, T: int, hyper, seed: int, rank: int = 0, world_size: int = 1,
                   parts: int = 1, free: bool = False, compact: bool = True, fused: bool = True,
                   price_unit_major: bool = False, metrics: bool = False, ep_len: int = 1, metric_slots: int = 1,
-                  hardcoded_agents=None) -> dict:
+                  hardcoded_agents=None, action_log=None) -> dict:
     """What a trainer must be for a checkpoint's state to fit it (compare_manifest's order of fields).
     hardcoded_agents: the rule-based agents of a mixed market, a field only when there are some (a file without
-    the field, as every file written before the field existed, has none)."""
+    the field, as every file written before the field existed, has none). action_log: "hist" or "tables" for a
+    trainer with the action log, a field only then, in the same way."""
     m = dict(format=FORMAT_VERSION, config=config_tensor(cfg), arch=str(arch), E=int(E), T=int(T))
     for f in dataclasses.fields(hyper):
         v = getattr(hyper, f.name)
@@ -107,6 +108,8 @@ def make_manifest(cfg: abi.MsConfig, arch: str, E: int, T: int, hyper, seed: int
              metrics=bool(metrics), ep_len=int(ep_len), metric_slots=int(metric_slots))
     if hardcoded_agents:
         m["hardcoded_agents"] = sorted(int(a) for a in hardcoded_agents)
+    if action_log:
+        m["action_log"] = str(action_log)
     return m
 
 
@@ -136,7 +139,14 @@ def compare_manifest(want: dict, got: dict, fields=None) -> None:
 def trainer_manifest(tr) -> dict:
     return make_manifest(tr.cfg, tr.arch, tr.E, tr.T, tr.hp, tr.seed, tr.rank, tr.world_size, len(tr.env.parts),
                          tr.free, tr.compact, tr.fused, bool(getattr(tr, "price_unit_major", False)),
-                         tr.metric_bufs is not None, tr.ep_len, tr.metric_slots, getattr(tr, "hardcoded", None))
+                         tr.metric_bufs is not None, tr.ep_len, tr.metric_slots, getattr(tr, "hardcoded", None),
+                         action_log_mode(tr))
+
+
+def action_log_mode(tr):
+    """The manifest's action_log of a trainer: None (no log), "hist" or "tables"."""
+    alog = getattr(tr, "_alog", None)
+    return None if alog is None else "tables" if alog.tables else "hist"
 
 
 # ---- plain-data encoding of the episode log (numpy arrays are not weights_only data)
@@ -209,6 +219,9 @@ def save(tr, path: str) -> dict:
     if tr.metric_bufs is not None:
         state["metric_bufs"] = [b.cpu() for b in tr.metric_bufs]
         state["episode_log"] = _encode(tr.episode_log)
+    if action_log_mode(tr):  # the open slots' counters and the episodes read so far (fields only with the log)
+        state["action_counters"] = tr._alog.state()
+        state["action_log"] = _encode(tr.action_log)
     torch.cuda.synchronize(dev)
     t2 = time.perf_counter()
     write_file(path, trainer_manifest(tr), state)
@@ -245,6 +258,9 @@ def load(tr, path: str) -> dict:
     mine, theirs = want.get("hardcoded_agents") or [], manifest.get("hardcoded_agents") or []
     if list(mine) != list(theirs):  # (an absent field: no rule-based agents)
         raise ValueError("checkpoint does not fit: hardcoded_agents is %r, the trainer's is %r" % (theirs, mine))
+    mine, theirs = want.get("action_log"), manifest.get("action_log")
+    if mine != theirs:  # (an absent field: no action log)
+        raise ValueError("checkpoint does not fit: action_log is %r, the trainer's is %r" % (theirs, mine))
     compare_manifest(want, manifest)
     units = tr.units()
     if set(state["units"]) != {u.name for u in units} or len(state["env"]) != len(tr.env.parts):
@@ -286,6 +302,10 @@ def load(tr, path: str) -> dict:
         for b, s in zip(tr.metric_bufs, state["metric_bufs"]):
             b.copy_(s)
         tr.episode_log[:] = _decode(state["episode_log"])  # in place: the trainer's EpisodeLog appends to this list
+    if action_log_mode(tr):
+        tr._alog.load_state(state["action_counters"])
+        tr.action_log[:] = _decode(state["action_log"])  # in place: the trainer's ActionLog appends to this list
+        tr._actions_logged = tr.rounds_done  # the rings belong to no rollout of this state
     tr._policy_version += 1   # the acting tables are rebuilt from the loaded policy_old
     tr._rings_pending = False  # the rings belong to no rollout of this state
     tr._offers_pending = False

@@ -18,6 +18,7 @@
 #include "ms_act_args.h"
 #include "ms_evaluate.h"
 #include "ms_action_hist.h"
+#include "ms_action_table.h"
 #include "ms_returns.h"
 #include "ms_dqn.h"
 #include "ms_bdqn.h"
@@ -1041,6 +1042,42 @@ int ms_action_hist(const ms_action_hist_args* g, void* stream) {
     const hipError_t e = ms::launch_action_hist(a, (hipStream_t)stream);
     if (e == hipErrorInvalidValue) return bad("too many rows for one launch");
     if (e != hipSuccess) return fail(MS_EHIP, "ms_action_hist: %s", hipGetErrorString(e));
+    return MS_OK;
+}
+
+int ms_action_table(const ms_action_table_args* g, void* stream) {
+    auto bad = [&](const char* why) { return fail(MS_EINVAL, "ms_action_table: %s", why); };
+    if (!g) return bad("args is NULL");
+    if (!g->actions || !g->keys || !g->counts) return bad("actions / keys / counts is NULL");
+    if (g->n_actions < 1 || g->n_actions > ms::kTableMaxActions)
+        return fail(MS_EINVAL, "ms_action_table: n_actions %d outside [1, %d]", g->n_actions, ms::kTableMaxActions);
+    if (g->n_keys < 1 || g->n_keys > ms::kTableMaxKeys)
+        return fail(MS_EINVAL, "ms_action_table: n_keys %d outside [1, %d]", g->n_keys, ms::kTableMaxKeys);
+    if (g->key_min < -128 || g->key_min > 127) return bad("key_min outside [-128, 127]");
+    if (g->n_units < 1 || g->units_per_bin < 1 || g->n_units % g->units_per_bin != 0)
+        return fail(MS_EINVAL, "ms_action_table: units_per_bin %d must be >= 1 and divide n_units %d", g->units_per_bin,
+                    g->n_units);
+    if (g->n_envs < 1 || g->n_rounds < 1 || g->episode_length < 1 || g->n_slots < 1)
+        return bad("n_envs, n_rounds, episode_length and n_slots must be >= 1");
+    if (g->round0 < 0) return bad("round0 must be >= 0");
+    if (g->row_stride < 1 || g->unit_stride < 1 || g->key_row_stride < 1 || g->key_unit_stride < 1)
+        return bad("strides must be >= 1");
+    const int64_t bins = g->n_units / g->units_per_bin;
+    if (bins * g->n_keys * g->n_actions > ms::kTableMaxCounters)
+        return fail(MS_EINVAL, "ms_action_table: %lld bins x %d keys x %d actions do not fit the %d counters a workgroup keeps",
+                    (long long)bins, g->n_keys, g->n_actions, ms::kTableMaxCounters);
+    ms::ActionTable a{};
+    a.actions = g->actions, a.row_stride = g->row_stride, a.unit_stride = g->unit_stride;
+    a.keys = g->keys, a.key_row_stride = g->key_row_stride, a.key_unit_stride = g->key_unit_stride;
+    a.n_units = g->n_units, a.units_per_bin = g->units_per_bin, a.n_bins = (int)bins;
+    a.n_keys = g->n_keys, a.key_min = g->key_min, a.n_actions = g->n_actions;
+    a.E = g->n_envs, a.n_rounds = g->n_rounds, a.episode_length = g->episode_length, a.n_slots = g->n_slots;
+    a.round0 = g->round0;
+    a.counts = reinterpret_cast<unsigned long long*>(g->counts);
+    a.skipped = reinterpret_cast<unsigned long long*>(g->skipped), a.bad = reinterpret_cast<unsigned long long*>(g->bad);
+    const hipError_t e = ms::launch_action_table(a, (hipStream_t)stream);
+    if (e == hipErrorInvalidValue) return bad("too many rows for one launch");
+    if (e != hipSuccess) return fail(MS_EHIP, "ms_action_table: %s", hipGetErrorString(e));
     return MS_OK;
 }
 

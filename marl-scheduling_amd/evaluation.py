@@ -6,6 +6,7 @@ import numpy as np
 import torch
 
 from . import metrics as mx
+from .action_log import ActionLog, n_priorities
 from .env import BatchedEnv
 from .episode_log import EpisodeLog
 from .ppo import act_round_free, act_round_greedy, offer_act_free
@@ -138,8 +139,13 @@ def _act(tr, b: dict, mode: str, t: int, philox_seed: int):
 
 
 @torch.no_grad()
-def evaluate(tr, episodes=1, n_envs=None, mode="greedy", seed=None, trace=False, hardcoded_agents=None) -> dict:
+def evaluate(tr, episodes=1, n_envs=None, mode="greedy", seed=None, trace=False, hardcoded_agents=None,
+             action_log=False, action_tables=False) -> dict:
     """Trainer.evaluate (its docstring is the contract)."""
+    if action_tables and not action_log:
+        raise ValueError("action_tables needs action_log=True")
+    if action_log and mode == "hardcoded":
+        raise ValueError("action_log counts action tensors, and mode 'hardcoded' has none")
     if tr.free and (mode == "hardcoded" or hardcoded_agents is not None):
         raise ValueError("the hard-coded agents act under fixed prices only")
     if mode == "hardcoded" and hardcoded_agents is not None:
@@ -156,8 +162,35 @@ def evaluate(tr, episodes=1, n_envs=None, mode="greedy", seed=None, trace=False,
     if hc is not None:  # the actions the rounds used (the rules' picks in the given agents' rows)
         taken = dict(acceptor=torch.empty_like(b["acc_action"]), offer_core=torch.empty_like(b["off_action"]))
 
+    alog = None
+    if action_log:  # counters of this call's own, a slot per episode
+        alog = ActionLog(N, C, L, tr.env.shape, n_priorities(tr.cfg), tr.free, tr.compact, action_tables, episodes,
+                         log.ep_len, tr.device)
+
+    # a mixed round's actions exist only after its env step, which rewrites the observations in place: the owners
+    # and the offer slots' priorities the round acted on are kept aside
+    kept = None
+    if alog is not None and hc is not None:
+        kept = dict(owner=torch.empty_like(b["core_owner"]) if tr.compact else None,
+                    offer_key=torch.empty_like(b["offer"][:, :, 2 * C], memory_format=torch.contiguous_format))
+
+    def count_round(t):
+        """Round t's actions into the action log."""
+        if kept is None:  # before the env step: b holds what the round acted on
+            acc, off, owner = b["acc_action"], b["off_action"], b["core_owner"] if tr.compact else None
+            keys = dict(offer_key=b["offer"][:, :, 2 * C], price_key=b["price_state"][:, :, 2] if tr.free else None)
+        else:
+            acc, off, owner = taken["acceptor"], taken["offer_core"], kept["owner"]
+            keys = dict(offer_key=kept["offer_key"])
+        alog.add(t, off, [(0, 1, acc, owner)], b["price_action"] if tr.free else None,
+                 **(keys if action_tables else {}))
+
     def one_round(t):
         acts = (None, None, None)
+        if kept is not None:
+            if kept["owner"] is not None:
+                kept["owner"].copy_(b["core_owner"])
+            kept["offer_key"].copy_(b["offer"][:, :, 2 * C])
         if mode != "hardcoded":
             _act(tr, b, mode, t, philox_seed)
             acts = (b["acc_action"].view(E, N, C), b["off_action"].view(E, N, L),
@@ -171,9 +204,13 @@ def evaluate(tr, episodes=1, n_envs=None, mode="greedy", seed=None, trace=False,
                                offer_price=b["env_price"].cpu())
             rounds.append(rec)
         if hc is None:
+            if alog is not None:
+                count_round(t)
             env.step(*acts, obs=obs, rewards=b["rewards"], events=log.events[0])
             return
         env.step_mixed(acts[0], acts[1], hc, obs=obs, rewards=b["rewards"], events=log.events[0], taken=taken)
+        if alog is not None:
+            count_round(t)
         if trace:
             rec.update(acceptor_action=taken["acceptor"].cpu(), offer_action=taken["offer_core"].cpu())
 
@@ -181,4 +218,7 @@ def evaluate(tr, episodes=1, n_envs=None, mode="greedy", seed=None, trace=False,
     if hc is not None:
         res["hardcoded_agents"] = hc
         split_sides(res["episodes"], hc)
+    if alog is not None:
+        alog.harvest(episodes * log.ep_len)
+        res["action_log"] = alog.episodes
     return dict(res, trace=rounds) if trace else res

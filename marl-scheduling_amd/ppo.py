@@ -442,6 +442,38 @@ def action_hist(actions, counts, round0: int, episode_length: int, gate=None, ow
     check(lib.ms_action_hist(ct.byref(g), stream_ptr(stream)))
 
 
+@torch.no_grad()
+def action_table(actions, keys, counts, round0: int, episode_length: int, units_per_bin: int = 1, key_min: int = 0,
+                 skipped=None, bad=None, stream=None):
+    """counts += the per-episode joint histogram of (key, action) (ms_action_table): actions and keys int8 [T, E, U]
+    (or [E, U]: one round), counts int64 [n_slots, U // units_per_bin, n_keys, n_actions]; round t of the call is
+    round round0 + t of the run and lands in slot ((round0 + t) // episode_length) % n_slots. Exact (integers), never
+    zeroes counts. An element whose key - key_min is outside [0, n_keys) is skipped (skipped, int64 [1], optional,
+    += 1) and its action is not looked at; under a key in range an action outside [0, n_actions) is not binned (bad,
+    int64 [1], optional, += 1). The tensors may be strided views: unit-major rings, price_obs[..., 2], the bytes of
+    off_pair, byte 2C of the offer rows."""
+    if not has("ms_action_table"):
+        raise RuntimeError("the loaded libmarlsched.so has no ms_action_table (built before it)")
+    if actions.dim() == 2:
+        actions, keys = actions.unsqueeze(0), keys.unsqueeze(0)
+    T, E, U = actions.shape
+    assert keys.shape == actions.shape
+    assert counts.dtype == torch.int64 and counts.is_contiguous() and counts.dim() == 4
+    n_slots, n_bins, K, A = counts.shape
+    assert units_per_bin >= 1 and n_bins * units_per_bin == U, "counts holds U / units_per_bin bins"
+    g = abi.MsActionTableArgs()
+    g.actions, (g.row_stride, g.unit_stride) = ptr(actions), _hist_rows(actions, "actions")
+    g.keys, (g.key_row_stride, g.key_unit_stride) = ptr(keys), _hist_rows(keys, "keys")
+    g.n_units, g.units_per_bin, g.n_keys, g.key_min, g.n_actions = U, int(units_per_bin), K, int(key_min), A
+    g.n_envs, g.round0, g.n_rounds, g.episode_length, g.n_slots = E, int(round0), T, int(episode_length), n_slots
+    g.counts = ptr(counts)
+    for name, x in (("skipped", skipped), ("bad", bad)):
+        if x is not None:
+            assert x.dtype == torch.int64 and x.numel() == 1
+            setattr(g, name, ptr(x))
+    check(lib.ms_action_table(ct.byref(g), stream_ptr(stream)))
+
+
 def _check_price_out(out, E: int, U: int, pus: int):
     """The price chooser's outputs: [E, U(, 4)] contiguous (pus = 0), or unit-major [U, E(, 4)] views
     whose unit stride (in rows) is pus."""

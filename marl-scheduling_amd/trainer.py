@@ -31,8 +31,10 @@ import torch
 
 from . import abi, evaluation
 from ._lib import ABI_LOADED, capturing, has, hip_capture, ptr
+from .action_log import ActionLog, n_priorities
 from .env import BatchedEnv
 from .episode_log import EpisodeLogging
+from .metrics import action_args as mx_action_args
 from .evaluation import env_seed  # (its home; dqn.py, aggregated.py and the tests take it from here too)
 from .ppo import (ActFrag, PPOGroup, PriceTable, act_round_free, combine_losses, discounted_returns, offer_act_free,
                   offer_compress, offer_expand, reference_init_order, reference_nets, unit_returns)
@@ -157,8 +159,15 @@ class Trainer(EpisodeLogging):
     def __init__(self, cfg: abi.MsConfig, n_envs: int, arch: str = "local", hyper: Hyper | None = None, seed: int = 0,
                  device=None, rank: int = 0, world_size: int = 1, process_group=None, fused: bool = True,
                  use_graph: bool = True, common_rows: bool = True, rollout_streams: int = 1, metrics: bool = False,
-                 episode_length: int | None = None, compact: bool = True, hardcoded_agents=None, diagnostics: int = 0):
-        """diagnostics (k >= 0): the number of ring slots update_diagnostics() evaluates after each update,
+                 episode_length: int | None = None, compact: bool = True, hardcoded_agents=None, diagnostics: int = 0,
+                 action_log: bool = False, action_tables: bool = False):
+        """action_log: one entry per finished episode in self.action_log (action_log.py: the histograms of the offer,
+        price and acceptor actions, pooled over the replicas), counted from the rollout's rings by log_actions(),
+        which iteration() calls between the rollout and the update. action_tables (needs action_log: ValueError
+        otherwise) adds the action-by-priority tables to each entry. Both off (the default): nothing is allocated,
+        launched or synchronised. hardcoded_agents' rows count what the rules played (the rings hold it). Several
+        ranks: each keeps the log of its own replicas.
+        diagnostics (k >= 0): the number of ring slots update_diagnostics() evaluates after each update,
         slots (2 i + 1) T // (2 k) for i < min(k, T); with k > 0 iteration() calls it after the update's end event
         and appends the result to self.diagnostics_log. 0 (the default) is off: nothing is allocated or launched.
         The log is not written into checkpoints (the checkpoint format does not know it): a resumed run starts an
@@ -317,6 +326,17 @@ class Trainer(EpisodeLogging):
         self._init_episode_log(metrics, [env for env, _, _ in self.env.parts], slots=self.metric_slots, hook=split,
                                episodeLength=self.ep_len, UPDATE_STEP=T, n_envs=self.E * world_size)
         self.metric_bufs = self._elog.bufs if metrics else None  # one per part; the captured rollouts hold them
+        # the action log (action_log.py): per-episode counters with the episode log's slots; log_actions() fills
+        # them from the rings after a rollout, outside the captured graphs (round0 changes from rollout to rollout)
+        if action_tables and not action_log:
+            raise ValueError("action_tables needs action_log=True")
+        self.action_log = []
+        self._alog = None
+        self._actions_logged = 0  # rounds_done at the last log_actions()
+        if action_log:
+            self._alog = ActionLog(N, C, L, s, n_priorities(cfg), self.free, self.compact, action_tables,
+                                   self.metric_slots, self.ep_len, dev, log=self.action_log)
+            self.action_log_info = self._alog.info
         # one rank: each unit type's update on its own stream (MS_UPDATE_STREAMS=0: one stream). Round 4: the
         # update 10.06 -> 9.63 ms but the next rollout 14.50 -> 15.63 ms (every rollout launch slower after a
         # multi-stream update graph), so it was off. Round 6, with cfg3's rollout one launch: update 8.50 -> 8.05 ms,
@@ -776,6 +796,47 @@ class Trainer(EpisodeLogging):
         self._offers_pending = self.off_compact
         self.rounds_done += self.T
 
+    # ---- action log
+    def log_actions(self, harvest: bool = True):
+        """The last rollout's actions into the action log's counters: eager launches on the current stream, reading
+        the rings as the rollout left them (nothing is completed or expanded for it). Call it once after every
+        rollout() and before update(), whose carry overwrites ring slot 0 of the observations (iteration() does);
+        a second call for the same rollout, a call before the first rollout and a trainer without action_log do
+        nothing. harvest: also read the episodes finished by now into self.action_log."""
+        if self._alog is None or self._actions_logged == self.rounds_done:
+            return
+        T, N, C, L = self.T, self.N, self.C, self.L
+        own = self.acc_owner[:T] if self.compact else None
+        ring = self.acc.actions_raw
+        if self._rings_pending:
+            # the acceptor ring holds slot 0 only (ms_act_round_free wrote it whole); the owners' items of the later
+            # rounds are by core in acc_own
+            acceptor = [(0, 1, ring[:1], own[:1]), (1, T, self.acc_own[0][1:], own[1:])]
+        else:
+            acceptor = [(0, T, ring, own)]
+        price = offer_key = price_key = None
+        if self.free:
+            price = self.price.actions_raw
+        if self._alog.tables:
+            if self.off_compact:  # the slot's (priority, remaining) pair: the priority is its first byte
+                offer_key = self.off_pair.view(torch.int8).view(T + 1, self.E, N * L, 2)[:T, :, :, 0]
+            else:
+                offer_key = self._off_obs[:T, :, :, 2 * C]
+            if self.free:
+                price_key = self.price_obs[..., 2]
+        self._alog.add(self.rounds_done - T, self.off.actions_raw, acceptor, price, offer_key, price_key)
+        self._actions_logged = self.rounds_done
+        if harvest:
+            self._alog.harvest(self.rounds_done)
+
+    def args_dict(self, replica="mean", params=None):
+        """EpisodeLogging.args_dict; with action_log also Experiment 3's keys "0" .. str(L - 1): agent 0's mean
+        offer action per slot and episode (metrics.action_args)."""
+        d = super().args_dict(replica, params)
+        if self._alog is not None:
+            d.update(mx_action_args(self.action_log, 0, self.L))
+        return d
+
     # ---- update
     def _draws(self, device=None):
         """Sub-unit selections, in the reference's random.randint order."""
@@ -1192,14 +1253,23 @@ class Trainer(EpisodeLogging):
         ev[0].record()
         self.rollout(defer_common=True)
         ev[1].record()
+        if self._alog is not None:
+            # the action log reads the rings while they are the rollout's (the update's carry rewrites the
+            # observations' slot 0), after the rollout's end event and before the update's start event: neither
+            # span of `timings` sees it
+            self.log_actions(harvest=False)
+            ev.insert(2, torch.cuda.Event(enable_timing=True))
+            ev[2].record()
         losses = self.update()
-        ev[2].record()
+        ev[-1].record()
         self._pending_events.append(ev)
         self.iterations += 1
         if self.diagnostics:  # after the update's end event: the rollout and update spans do not see it
             self.diagnostics_log.append(self.update_diagnostics())
         if self._elog is not None:  # the episodes finished by now (trainPPO.py:200-226), into self.episode_log
             self._elog.harvest(self.rounds_done)
+        if self._alog is not None:
+            self._alog.harvest(self.rounds_done)
         return losses
 
     # ---- evaluation (evaluation.py)
@@ -1210,7 +1280,8 @@ class Trainer(EpisodeLogging):
         return evaluation.eval_seed(self.seed, self.rank, int(n_envs or self.E))
 
     def evaluate(self, episodes: int = 1, n_envs: int | None = None, mode: str = "greedy", seed: int | None = None,
-                 trace: bool = False, hardcoded_agents=None) -> dict:
+                 trace: bool = False, hardcoded_agents=None, action_log: bool = False,
+                 action_tables: bool = False) -> dict:
         """Evaluate the current policy (policy_old, the nets the next rollout acts with) for `episodes` episodes
         of episode_length rounds on n_envs (default: E) fresh replicas of their own; replica e is seeded
         seed + e (default seed: eval_seed()). Training state is left untouched: the training env, the rings,
@@ -1233,6 +1304,12 @@ class Trainer(EpisodeLogging):
         ValueError with mode "hardcoded", under free prices and for an index outside [0, N). None (the default)
         leaves the call and its result's keys as they are without the argument.
 
+        action_log: the result gains action_log, a list with one entry per episode with the keys of
+        Trainer(action_log=True)'s entries (action_log.py), counted round by round from the evaluation's own action
+        tensors (with hardcoded_agents: from the actions the rounds used); acceptors by core owner where the
+        buffers hold owners, else every unit. action_tables (needs action_log) adds the action-by-priority tables.
+        ValueError with mode "hardcoded" (no action tensors exist there). The training log is not touched.
+
         Eager launches on the current stream (one act launch and one env round per round). Each call steps a
         newly created env (an env's reset re-emits observations; it does not rewind the world or its job
         stream), so equal arguments give equal results; the tensors are kept between calls, and the last env
@@ -1240,7 +1317,8 @@ class Trainer(EpisodeLogging):
         Returns dict(mode, seed, n_envs, episodes=[metrics.reduce_replicas(ep), ...] (the argsDict values
         Plot.py reads, averaged over replicas), per_replica=[[dict per replica] per episode]); with trace also
         trace=[per round: the observations acted on and every action array fed to the env, CPU tensors]."""
-        return evaluation.evaluate(self, episodes, n_envs, mode, seed, trace, hardcoded_agents)
+        return evaluation.evaluate(self, episodes, n_envs, mode, seed, trace, hardcoded_agents, action_log,
+                                   action_tables)
 
     # ---- checkpoints (checkpoint.py)
     def save_checkpoint(self, path: str) -> dict:
@@ -1268,9 +1346,9 @@ class Trainer(EpisodeLogging):
     @property
     def timings(self):
         for ev in self._pending_events:
-            ev[2].synchronize()
+            ev[-1].synchronize()  # (with the action log: [rollout start, rollout end, update start, update end])
             self._timings["rollout"] += ev[0].elapsed_time(ev[1]) / 1e3
-            self._timings["update"] += ev[1].elapsed_time(ev[2]) / 1e3
+            self._timings["update"] += ev[-2].elapsed_time(ev[-1]) / 1e3
         self._pending_events = []
         return self._timings
 
