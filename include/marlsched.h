@@ -650,6 +650,50 @@ int ms_env_rollout_act_mixed(ms_env* env, const ms_actions* act, const ms_obs_ou
                              const ms_event_out* ev, const ms_fused_act* next, const ms_round_strides* strides,
                              int32_t n_rounds, int32_t act_after_last, uint64_t hc_mask, void* stream);
 
+/* A learned auctioneer in the fixed-price fused launches (added without an ABI step: look the names up). The
+ * auctioneer is a third net of the acceptor's shape (acc_obs_dim inputs, max_offers + 1 actions), one net shared by
+ * the C cores, that acts for the cores nobody owns (SchedulingEnv.step's auctioneer_action; its observation,
+ * gatherDividedAuctioneerObservation, is core row c where core_owner[c] == 0 and the foreign row otherwise).
+ * The calls are ms_env_step_act / ms_env_rollout_act with act->auctioneer given, so the round draws no tie-break
+ * from the env stream, and with the auctioneer's acting after the offer units' and the acceptors': item e * C + c
+ * samples like an acceptor item of ms_policy_act_compact(core_rows, core_owner == 0, n_units = C), with
+ * auct_offset as that call's offset and next->seed / next->offset_dev / next->common_row shared with the two other
+ * nets. Outputs equal those of that call on the emitted observations bit for bit. */
+typedef struct ms_fused_act_auct {
+    ms_mlp_params auctioneer; /* n_groups 1, act_frag with the common row's table; row_base its Philox row base */
+    uint64_t auct_offset;
+    int8_t* auct_action;      /* [E][C] */
+    float* auct_logprob;      /* [E][C] */
+} ms_fused_act_auct;
+
+/* Per-round byte strides of ms_env_rollout_act_auct's own arrays (beside ms_round_strides; the acting after round
+ * t draws with auct_offset + t * strides->offset_step). */
+typedef struct ms_round_strides_auct {
+    int64_t auctioneer_action;                  /* ms_actions auctioneer */
+    int64_t next_auct_action, next_auct_logprob; /* ms_fused_act_auct outputs */
+} ms_round_strides_auct;
+
+/* 1 when the two calls below can run this env's rounds (what ms_env_step_act_supported asks), else 0. */
+int ms_env_auct_supported(const ms_env* env);
+
+/* ms_env_step_act with act->auctioneer as the round's auctioneer actions and the auctioneer's next acting.
+ * MS_EINVAL with a message, launching nothing: a free-price env, a NULL action array or output (act->auctioneer
+ * included), an unsupported shape, an auctioneer net that is not one 32-input k-step with at most 16 actions
+ * of the acceptor's shape with act fragments, and whatever ms_env_step_act refuses. */
+int ms_env_step_act_auct(ms_env* env, const ms_actions* act, const ms_obs_out* obs, const ms_reward_out* rew,
+                         const ms_event_out* ev, const ms_fused_act* next, const ms_fused_act_auct* auct,
+                         void* stream);
+
+/* n_rounds consecutive ms_env_step_act_auct calls in one launch, as ms_env_rollout_act runs ms_env_step_act's:
+ * round t reads act->auctioneer advanced by t * astrides->auctioneer_action bytes, and the acting after it writes
+ * auct's outputs advanced by t strides; rew->auctioneer advances by strides->auctioneer_reward. When the action
+ * ring is also the acting's output ring, round t + 1 plays what the acting after round t sampled. Bit-identical to
+ * the n_rounds separate calls; the same refusals, plus ms_env_rollout_act's. */
+int ms_env_rollout_act_auct(ms_env* env, const ms_actions* act, const ms_obs_out* obs, const ms_reward_out* rew,
+                            const ms_event_out* ev, const ms_fused_act* next, const ms_fused_act_auct* auct,
+                            const ms_round_strides* strides, const ms_round_strides_auct* astrides,
+                            int32_t n_rounds, int32_t act_after_last, void* stream);
+
 /* ABI 17: the locally shared free-price rollout (BASELINE cfg3; LocallySharedPPO + FreePriceOfferPPO, DESIGN
  * §1) in one launch: every round's getActionForAllAgents (SchedulingEnvironment.py:150-172) fused after the env
  * round that built its observations. A workgroup steps 4 * N replicas (16 lanes each) and then acts for them

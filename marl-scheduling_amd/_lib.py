@@ -159,6 +159,16 @@ def _load():
         "ms_ppo_grad_offer_compact": (ct.c_int, [ct.POINTER(abi.MsMlpParams), ct.POINTER(abi.MsMlpParams),
                                                  ct.POINTER(abi.MsPpoBatch), P, P, ct.c_float, P, ct.c_size_t,
                                                  ct.POINTER(abi.MsPpoGrads), P]),
+        # the fused launches with a learned auctioneer (Trainer(learned_auctioneer=True))
+        "ms_env_auct_supported": (ct.c_int, [P]),
+        "ms_env_step_act_auct": (ct.c_int, [P, ct.POINTER(abi.MsActions), ct.POINTER(abi.MsObsOut),
+                                            ct.POINTER(abi.MsRewardOut), ct.POINTER(abi.MsEventOut),
+                                            ct.POINTER(abi.MsFusedAct), ct.POINTER(abi.MsFusedActAuct), P]),
+        "ms_env_rollout_act_auct": (ct.c_int, [P, ct.POINTER(abi.MsActions), ct.POINTER(abi.MsObsOut),
+                                               ct.POINTER(abi.MsRewardOut), ct.POINTER(abi.MsEventOut),
+                                               ct.POINTER(abi.MsFusedAct), ct.POINTER(abi.MsFusedActAuct),
+                                               ct.POINTER(abi.MsRoundStrides), ct.POINTER(abi.MsRoundStridesAuct),
+                                               i32, i32, P]),
     }
     sig.update({name: v for name, v in optional.items() if hasattr(L, name)})
     L.ms_abi_version.restype = ct.c_int
@@ -222,6 +232,7 @@ EXPORTED = (
     "ms_wide_grad",
     "ms_env_rollout_act_free_compact", "ms_offer_compress", "ms_offer_expand", "ms_ppo_grad_offer_compact",
     "ms_action_hist", "ms_wide_act_greedy", "ms_action_table",
+    "ms_env_auct_supported", "ms_env_step_act_auct", "ms_env_rollout_act_auct",
 )
 
 

@@ -217,6 +217,15 @@ class MsRoundStrides(ct.Structure):  # ms_round_strides (ABI 16): bytes per roun
                                           "next_acc_logprob")] + [("offset_step", ct.c_uint64)]
 
 
+class MsFusedActAuct(ct.Structure):  # ms_fused_act_auct: the learned auctioneer's acting beside an MsFusedAct
+    _fields_ = [("auctioneer", MsMlpParams), ("auct_offset", ct.c_uint64), ("auct_action", ct.c_void_p),
+                ("auct_logprob", ct.c_void_p)]
+
+
+class MsRoundStridesAuct(ct.Structure):  # ms_round_strides_auct: bytes per round
+    _fields_ = [(n, ct.c_int64) for n in ("auctioneer_action", "next_auct_action", "next_auct_logprob")]
+
+
 class MsFusedActFree(ct.Structure):  # ms_fused_act_free (ABI 18: own_action / own_logprob)
     _fields_ = [("core_chooser", MsMlpParams), ("price_chooser", MsMlpParams), ("acceptor", MsMlpParams),
                 ("common_row", ct.c_void_p), ("price_table", ct.c_void_p), ("seed", ct.c_uint64),

@@ -17,7 +17,7 @@ HEADERS=("${HERE}"/csrc/*.h "${HERE}/../include/marlsched.h")  # every header: o
 CCVER="$("${HIPCC}" --version 2>/dev/null | head -3 | tr '\n' ' ')"
 objs=()
 pids=()
-for src in env_kernels.hip acc_fill_kernels.hip policy_kernels.hip act_pair_kernels.hip greedy_kernels.hip evaluate_kernels.hip action_hist_kernels.hip action_table_kernels.hip returns_kernels.hip ppo_kernels.hip agg_kernels.hip dqn_kernels.hip bdqn_kernels.hip bdqn_update_kernels.hip wide_kernels.hip snapshot_kernels.hip capi.cpp; do
+for src in env_kernels.hip env_auct_kernels.hip acc_fill_kernels.hip policy_kernels.hip act_pair_kernels.hip greedy_kernels.hip evaluate_kernels.hip action_hist_kernels.hip action_table_kernels.hip returns_kernels.hip ppo_kernels.hip agg_kernels.hip dqn_kernels.hip bdqn_kernels.hip bdqn_update_kernels.hip wide_kernels.hip snapshot_kernels.hip capi.cpp; do
   obj="${OBJDIR}/${src%.*}.o"
   # the env round reproduces Python's float64 arithmetic: no contraction there; the policy
   # and PPO kernels follow torch's f32 (which fuses freely) within tolerance: fma allowed

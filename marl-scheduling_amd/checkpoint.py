@@ -92,11 +92,12 @@ def config_of(t: torch.Tensor) -> abi.MsConfig:
 def make_manifest(cfg: abi.MsConfig, arch: str, E: int, T: int, hyper, seed: int, rank: int = 0, world_size: int = 1,
                   parts: int = 1, free: bool = False, compact: bool = True, fused: bool = True,
                   price_unit_major: bool = False, metrics: bool = False, ep_len: int = 1, metric_slots: int = 1,
-                  hardcoded_agents=None, action_log=None) -> dict:
+                  hardcoded_agents=None, action_log=None, learned_auctioneer: bool = False) -> dict:
     """What a trainer must be for a checkpoint's state to fit it (compare_manifest's order of fields).
     hardcoded_agents: the rule-based agents of a mixed market, a field only when there are some (a file without
     the field, as every file written before the field existed, has none). action_log: "hist" or "tables" for a
-    trainer with the action log, a field only then, in the same way."""
+    trainer with the action log, a field only then, in the same way. learned_auctioneer: True for a trainer with
+    the auctioneer's net, a field only then."""
     m = dict(format=FORMAT_VERSION, config=config_tensor(cfg), arch=str(arch), E=int(E), T=int(T))
     for f in dataclasses.fields(hyper):
         v = getattr(hyper, f.name)
@@ -110,6 +111,8 @@ def make_manifest(cfg: abi.MsConfig, arch: str, E: int, T: int, hyper, seed: int
         m["hardcoded_agents"] = sorted(int(a) for a in hardcoded_agents)
     if action_log:
         m["action_log"] = str(action_log)
+    if learned_auctioneer:
+        m["learned_auctioneer"] = True
     return m
 
 
@@ -140,7 +143,7 @@ def trainer_manifest(tr) -> dict:
     return make_manifest(tr.cfg, tr.arch, tr.E, tr.T, tr.hp, tr.seed, tr.rank, tr.world_size, len(tr.env.parts),
                          tr.free, tr.compact, tr.fused, bool(getattr(tr, "price_unit_major", False)),
                          tr.metric_bufs is not None, tr.ep_len, tr.metric_slots, getattr(tr, "hardcoded", None),
-                         action_log_mode(tr))
+                         action_log_mode(tr), getattr(tr, "auct", None) is not None)
 
 
 def action_log_mode(tr):
@@ -248,6 +251,12 @@ def _load_net(net, saved: dict):
         v.copy_(saved[k])
 
 
+def _check_auctioneer(want: dict, manifest: dict) -> None:
+    mine, theirs = bool(want.get("learned_auctioneer")), bool(manifest.get("learned_auctioneer"))
+    if mine != theirs:  # (an absent field: the rule-based auctioneer)
+        raise ValueError("checkpoint does not fit: learned_auctioneer is %r, the trainer's is %r" % (theirs, mine))
+
+
 @torch.no_grad()
 def load(tr, path: str) -> dict:
     """Trainer.load_checkpoint: the manifest must match (ValueError naming the first differing field, the
@@ -261,6 +270,7 @@ def load(tr, path: str) -> dict:
     mine, theirs = want.get("action_log"), manifest.get("action_log")
     if mine != theirs:  # (an absent field: no action log)
         raise ValueError("checkpoint does not fit: action_log is %r, the trainer's is %r" % (theirs, mine))
+    _check_auctioneer(want, manifest)
     compare_manifest(want, manifest)
     units = tr.units()
     if set(state["units"]) != {u.name for u in units} or len(state["env"]) != len(tr.env.parts):
@@ -331,6 +341,7 @@ def load_policy(tr, path: str) -> dict:
     with any E, T, seed or world size; the configuration's shape terms (agents, cores, collection length, price
     mode and the nets' dimensions they and the job priorities give), arch and free must be the trainer's. For evaluate() on a saved policy."""
     manifest, state = read_file(path)
+    _check_auctioneer(trainer_manifest(tr), manifest)
     compare_manifest(trainer_manifest(tr), manifest, fields=("format", "arch", "free"))
     theirs = config_of(manifest["config"])
     for f in POLICY_FIELDS:

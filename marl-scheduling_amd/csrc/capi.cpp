@@ -15,6 +15,7 @@
 
 #include "ms_layout.h"
 #include "ms_env_launch.h"
+#include "ms_env_auct_launch.h"
 #include "ms_act_args.h"
 #include "ms_evaluate.h"
 #include "ms_action_hist.h"
@@ -332,6 +333,77 @@ int ms_env_rollout_act_mixed(ms_env* env, const ms_actions* act, const ms_obs_ou
     const int rc = fused_mixed_check(env, act, hc_mask, "ms_env_rollout_act_mixed");
     if (rc != MS_OK) return rc;
     return rollout_act_impl(env, act, obs, rew, ev, next, strides, n_rounds, act_after_last, hc_mask, stream);
+}
+
+// ---- the fused launches with a learned auctioneer (env_auct_kernels.hip)
+int ms_env_auct_supported(const ms_env* env) { return ms_env_step_act_supported(env); }
+
+// the checks ms_env_step_act_auct and ms_env_rollout_act_auct share (before fused_act_args'); fills aa
+static int auct_act_args(const ms_env* env, const ms_actions* act, const ms_fused_act_auct* auct, const char* who,
+                         ms::AuctAct* aa) {
+    if (!env || !act || !auct) return fail(MS_EINVAL, "%s: env/actions/auct is NULL", who);
+    auto bad = [&](const char* why) { return fail(MS_EINVAL, "%s: %s", who, why); };
+    if (env->cfg.free_prices) return bad("the learned auctioneer is fixed-price only");
+    if (!act->acceptor || !act->offer_core || !act->auctioneer)
+        return bad("acceptor, offer_core and auctioneer actions must all be given");
+    if (!auct->auct_action || !auct->auct_logprob) return bad("NULL auctioneer output");
+    const ms::Params& P = env->P;
+    const ms_mlp_params& a = auct->auctioneer;
+    if (a.n_groups != 1 || a.hidden != 16 || !a.act_frag || a.in_dim != P.d_acc || a.n_actions != P.O + 1 ||
+        P.acc_stride > 32 || a.n_actions > 16)
+        return bad("the auctioneer net must be one 16-wide net of the acceptor's shape (one 32-input k-step, <= 16 "
+                   "actions) with act fragments");
+    if (!ms_env_step_act_supported(env)) return bad("shape not supported (one k-step, <= 16 actions, a wave's rows)");
+    *aa = ms::AuctAct{a, auct->auct_offset, auct->auct_action, auct->auct_logprob};
+    return MS_OK;
+}
+
+static int env_auct_impl(ms_env* env, const ms_actions* act, const ms_obs_out* obs, const ms_reward_out* rew,
+                         const ms_event_out* ev, const ms_fused_act* next, const ms_fused_act_auct* auct,
+                         const ms::AuctRollout* ro, const char* who, void* stream) {
+    ms::AuctAct aa;
+    int rc = auct_act_args(env, act, auct, who, &aa);
+    if (rc != MS_OK) return rc;
+    ms::FusedAct fa;
+    rc = fused_act_args(env, act, obs, ev, next, who, &fa);
+    if (rc != MS_OK) return rc;
+    if (__atomic_load_n(env->err_host, __ATOMIC_ACQUIRE))
+        return fail(MS_EOVERFLOW, "an earlier round raised a per-env error flag (see ms_env_flags)");
+    ms::StepIO io{};
+    rc = fill_io(env, act, obs, rew, ev, &io);
+    if (rc != MS_OK) return rc;
+    if (ro)
+        HIP_TRY(ms::launch_env_rollout_act_auct(*env, io, fa, aa, *ro, (hipStream_t)stream));
+    else
+        HIP_TRY(ms::launch_env_step_act_auct(*env, io, fa, aa, (hipStream_t)stream));
+    env->round += ro ? ro->n_rounds : 1;
+    return MS_OK;
+}
+
+int ms_env_step_act_auct(ms_env* env, const ms_actions* act, const ms_obs_out* obs, const ms_reward_out* rew,
+                         const ms_event_out* ev, const ms_fused_act* next, const ms_fused_act_auct* auct,
+                         void* stream) {
+    return env_auct_impl(env, act, obs, rew, ev, next, auct, nullptr, "ms_env_step_act_auct", stream);
+}
+
+int ms_env_rollout_act_auct(ms_env* env, const ms_actions* act, const ms_obs_out* obs, const ms_reward_out* rew,
+                            const ms_event_out* ev, const ms_fused_act* next, const ms_fused_act_auct* auct,
+                            const ms_round_strides* strides, const ms_round_strides_auct* astrides,
+                            int32_t n_rounds, int32_t act_after_last, void* stream) {
+    const char* who = "ms_env_rollout_act_auct";
+    if (!strides || !astrides || n_rounds < 1) return fail(MS_EINVAL, "%s: strides NULL or n_rounds < 1", who);
+    if (ev && (ev->accepted || ev->terminated))
+        return fail(MS_EINVAL, "%s: no accepted / terminated event records", who);
+    if (rew && (rew->price || rew->aggregated_offer || rew->aggregated_acceptor))
+        return fail(MS_EINVAL, "%s: no price / aggregated reward outputs", who);
+    const ms_round_strides& r = *strides;
+    const ms::AuctRollout ro{{r.acceptor_action, r.offer_action, r.core_rows, r.core_owner, r.offer_obs,
+                              r.offer_reward, r.acceptor_reward, r.agent_reward, r.auctioneer_reward,
+                              r.next_off_action, r.next_off_logprob, r.next_acc_action, r.next_acc_logprob,
+                              r.offset_step},
+                             astrides->auctioneer_action, astrides->next_auct_action, astrides->next_auct_logprob,
+                             n_rounds, act_after_last ? 1 : 0};
+    return env_auct_impl(env, act, obs, rew, ev, next, auct, &ro, who, stream);
 }
 
 int ms_env_step_act_supported(const ms_env* env) {

@@ -324,6 +324,48 @@ class BatchedEnv:
                                      ct.byref(next_act), ct.byref(strides), int(n_rounds), int(bool(act_after_last)),
                                      stream_ptr(stream)))
 
+    def auct_supported(self) -> bool:
+        """Whether step_act_auct / rollout_act_auct can run this env's rounds (ms_env_auct_supported; False for a
+        library built before the learned auctioneer)."""
+        return (has("ms_env_auct_supported") and has("ms_env_step_act_auct") and has("ms_env_rollout_act_auct") and
+                not self.free_prices and bool(lib.ms_env_auct_supported(self._h)))
+
+    def _auct_check(self, auctioneer, symbol: str):
+        if not has(symbol):
+            raise RuntimeError("the loaded libmarlsched.so has no %s" % symbol)
+        assert auctioneer is not None and auctioneer.dtype == torch.int8 and auctioneer.device == self.device
+
+    def step_act_auct(self, acceptor, offer_core, auctioneer, next_act, next_auct, obs, rewards, events=None,
+                      stream=None):
+        """step(next_act=...) with a learned auctioneer (ms_env_step_act_auct): the round plays auctioneer [E, C]
+        int8 for the cores nobody owns (no tie-break is drawn from the env stream), and next_auct (an
+        abi.MsFusedActAuct) is the auctioneer's next acting beside next_act's."""
+        self._auct_check(auctioneer, "ms_env_step_act_auct")
+        assert auctioneer.is_contiguous() and auctioneer.numel() == self.E * self.C
+        a, o, r, ev = self._step_structs(acceptor, offer_core, None, auctioneer, obs, rewards, events)
+        check(lib.ms_env_step_act_auct(self._h, ct.byref(a), ct.byref(o), ct.byref(r), ct.byref(ev) if ev else None,
+                                       ct.byref(next_act), ct.byref(next_auct), stream_ptr(stream)))
+
+    def rollout_act_auct(self, acceptor, offer_core, auctioneer, obs, rewards, next_act, next_auct, strides, astrides,
+                         n_rounds, act_after_last=False, events=None, stream=None, next_out=None):
+        """rollout_act with a learned auctioneer (ms_env_rollout_act_auct): n_rounds rounds of step_act_auct in one
+        launch. astrides (an abi.MsRoundStridesAuct): the bytes per round of auctioneer and of next_auct's outputs.
+        next_out: the tensors behind next_auct's outputs, dict(auct_action, auct_logprob) (round 0's slots),
+        bounds-checked like the other rings when given."""
+        self._auct_check(auctioneer, "ms_env_rollout_act_auct")
+        rings = self._ring_list(acceptor, offer_core, obs, rewards, strides)
+        rings.append((auctioneer, astrides.auctioneer_action, torch.int8))
+        self.check_rings(rings, n_rounds)
+        if next_out is not None and (n_rounds > 1 or act_after_last):
+            self.check_rings([(next_out["auct_action"], astrides.next_auct_action, torch.int8),
+                              (next_out["auct_logprob"], astrides.next_auct_logprob, torch.float32)],
+                             n_rounds if act_after_last else n_rounds - 1)
+        a, o, r, ev = self._step_structs(acceptor, offer_core, None, auctioneer, obs, rewards, events)
+        check(lib.ms_env_rollout_act_auct(self._h, ct.byref(a), ct.byref(o), ct.byref(r), ct.byref(ev) if ev else None,
+                                          ct.byref(next_act), ct.byref(next_auct), ct.byref(strides),
+                                          ct.byref(astrides), int(n_rounds), int(bool(act_after_last)),
+                                          stream_ptr(stream)))
+
     def rollout_act_free(self, acceptor, offer_core, obs, rewards, next_act, next_out, strides, n_rounds,
                          act_after_last=False, events=None, stream=None, compact=None):
         """A locally shared free-price rollout of n_rounds rounds in one launch (ms_env_rollout_act_free; BASELINE

@@ -140,8 +140,18 @@ def _act(tr, b: dict, mode: str, t: int, philox_seed: int):
 
 @torch.no_grad()
 def evaluate(tr, episodes=1, n_envs=None, mode="greedy", seed=None, trace=False, hardcoded_agents=None,
-             action_log=False, action_tables=False) -> dict:
+             action_log=False, action_tables=False, auctioneer=None) -> dict:
     """Trainer.evaluate (its docstring is the contract)."""
+    has_auct = getattr(tr, "auct", None) is not None
+    if auctioneer is None:
+        auctioneer = "learned" if (has_auct and mode != "hardcoded") else "hardcoded"
+    if auctioneer not in ("learned", "hardcoded"):
+        raise ValueError("auctioneer must be 'learned' or 'hardcoded'")
+    if auctioneer == "learned" and not has_auct:
+        raise ValueError("auctioneer='learned' needs a trainer built with learned_auctioneer=True")
+    if auctioneer == "learned" and mode == "hardcoded":
+        raise ValueError("auctioneer='learned' goes with mode 'greedy' or 'sample'")
+    learned_auct = auctioneer == "learned"
     if action_tables and not action_log:
         raise ValueError("action_tables needs action_log=True")
     if action_log and mode == "hardcoded":
@@ -156,6 +166,13 @@ def evaluate(tr, episodes=1, n_envs=None, mode="greedy", seed=None, trace=False,
     E, N, C, L = env.E, tr.N, tr.C, tr.L
     b = _buffers(tr, E)
     obs_keys = ("core_rows", "core_owner", "offer") if tr.compact else ("acceptor", "offer")
+    if learned_auct:  # the auctioneer rows [E][C][stride] beside the agents' observations, and its actions
+        if "auctioneer" not in b:
+            st = tr.env.shape.acc_obs_stride
+            b.update(auctioneer=torch.zeros((E, C, st), dtype=torch.int8, device=tr.device),
+                     auct_action=torch.zeros((E, C), dtype=torch.int8, device=tr.device),
+                     auct_logprob=torch.zeros((E, C), dtype=torch.float32, device=tr.device))
+        obs_keys = obs_keys + ("auctioneer",)
     obs = env.reset({k: b[k] for k in obs_keys})
     philox_seed = (seed * 7919) & 0xFFFFFFFFFFFFFFFF
     rounds = []
@@ -195,10 +212,22 @@ def evaluate(tr, episodes=1, n_envs=None, mode="greedy", seed=None, trace=False,
             _act(tr, b, mode, t, philox_seed)
             acts = (b["acc_action"].view(E, N, C), b["off_action"].view(E, N, L),
                     b["env_price"].view(E, N, L) if tr.free else None)
+        auct_act = None
+        if learned_auct:
+            net = tr.auct.group.policy_old
+            if mode == "greedy":
+                net.act_greedy(b["auctioneer"], C, common_row=tr.acc_common, action=b["auct_action"],
+                               logprob=b["auct_logprob"])
+            else:
+                net.act(b["auctioneer"], C, philox_seed, 8 * t + 5, action=b["auct_action"],
+                        logprob=b["auct_logprob"], common_row=tr.acc_common)
+            auct_act = b["auct_action"]
         if trace:
             rec = {k: b[k].cpu() for k in obs_keys}
             if mode != "hardcoded":
                 rec.update(acceptor_action=b["acc_action"].cpu(), offer_action=b["off_action"].cpu())
+                if learned_auct:
+                    rec.update(auctioneer_action=b["auct_action"].cpu())
                 if tr.free:
                     rec.update(price_state=b["price_state"].cpu(), price_action=b["price_action"].cpu(),
                                offer_price=b["env_price"].cpu())
@@ -206,15 +235,17 @@ def evaluate(tr, episodes=1, n_envs=None, mode="greedy", seed=None, trace=False,
         if hc is None:
             if alog is not None:
                 count_round(t)
-            env.step(*acts, obs=obs, rewards=b["rewards"], events=log.events[0])
+            env.step(*acts, auctioneer=auct_act, obs=obs, rewards=b["rewards"], events=log.events[0])
             return
-        env.step_mixed(acts[0], acts[1], hc, obs=obs, rewards=b["rewards"], events=log.events[0], taken=taken)
+        env.step_mixed(acts[0], acts[1], hc, auctioneer=auct_act, obs=obs, rewards=b["rewards"], events=log.events[0], taken=taken)
         if alog is not None:
             count_round(t)
         if trace:
             rec.update(acceptor_action=taken["acceptor"].cpu(), offer_action=taken["offer_core"].cpu())
 
     res = evaluation_result(mode, seed, E, run_episodes(log, episodes, one_round))
+    if has_auct or learned_auct:
+        res["auctioneer"] = auctioneer
     if hc is not None:
         res["hardcoded_agents"] = hc
         split_sides(res["episodes"], hc)

@@ -160,8 +160,17 @@ class Trainer(EpisodeLogging):
                  device=None, rank: int = 0, world_size: int = 1, process_group=None, fused: bool = True,
                  use_graph: bool = True, common_rows: bool = True, rollout_streams: int = 1, metrics: bool = False,
                  episode_length: int | None = None, compact: bool = True, hardcoded_agents=None, diagnostics: int = 0,
-                 action_log: bool = False, action_tables: bool = False):
-        """action_log: one entry per finished episode in self.action_log (action_log.py: the histograms of the offer,
+                 action_log: bool = False, action_tables: bool = False, learned_auctioneer: bool = False):
+        """learned_auctioneer (fixed prices; off by default: nothing is allocated, launched or changed): a fourth unit
+        type "auctioneer" (self.auct), one net of the acceptor's shape shared by the C cores, that acts every round
+        for the cores nobody owns in place of the in-kernel HardcodedAuctioneerAcceptor and trains in update() on
+        the per-core auctioneerReward like the other units (centralisation_sample cores drawn per update, after the
+        offer draws). Its initial weights are drawn after every agent net's, so a seeded trainer's agent nets start
+        as without it. Its states are the compact acceptor rows with core_owner == 0 as the owner (the auctioneer
+        row of core c is core row c where nobody owns it, else the foreign row). ValueError under free prices, with
+        compact=False, with hardcoded_agents, with world_size > 1 and with diagnostics > 0. action_log keeps
+        counting the agents' units only.
+        action_log: one entry per finished episode in self.action_log (action_log.py: the histograms of the offer,
         price and acceptor actions, pooled over the replicas), counted from the rollout's rings by log_actions(),
         which iteration() calls between the rollout and the update. action_tables (needs action_log: ValueError
         otherwise) adds the action-by-priority tables to each entry. Both off (the default): nothing is allocated,
@@ -180,6 +189,17 @@ class Trainer(EpisodeLogging):
         changes nothing; an empty list is a trainer without the argument, bit for bit. ValueError under free
         prices, for an index outside [0, N) and for a mask that leaves no agent to train."""
         assert arch in ("divided", "local", "global")
+        if learned_auctioneer:  # (before anything touches the device)
+            if cfg.free_prices:
+                raise ValueError("learned_auctioneer acts under fixed prices only")
+            if not compact or not common_rows or abi.config_shape(cfg)["acc_obs_stride"] < 16:
+                raise ValueError("learned_auctioneer needs the compact acceptor observations (compact=True)")
+            if hardcoded_agents is not None:
+                raise ValueError("learned_auctioneer does not go with hardcoded_agents")
+            if world_size > 1:
+                raise ValueError("learned_auctioneer runs on one rank (world_size == 1)")
+            if int(diagnostics) > 0:
+                raise ValueError("learned_auctioneer has no update diagnostics (diagnostics == 0)")
         self.fused = fused  # fused HIP gradient (ms_ppo_grad) vs torch autograd
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         torch.cuda.set_device(self.device)
@@ -251,6 +271,13 @@ class Trainer(EpisodeLogging):
             self.price = _Unit("price", self.E, T, N * L, (N * L) // go, 4, 4, s.price_actions,
                                mk(go, 4, s.price_actions, hp.offer_gamma, k_off, nets["price"]), dev, torch.float32,
                                unit_major=self.price_unit_major)
+        # the learned auctioneer: one net of the acceptor's shape for the C cores, drawn after every agent net
+        self.auct = None
+        if learned_auctioneer:
+            auct_net = reference_nets(["acc"], dict(acc=dims["acc"]))["acc"]
+            self.auct = _Unit("auctioneer", self.E, T, C, C, s.acc_obs_dim, s.acc_obs_stride, s.acc_actions,
+                              mk(1, s.acc_obs_dim, s.acc_actions, acc_gamma, _k_epochs(hp.raw_k_epochs, C), auct_net),
+                              dev, torch.int32)
         # the masked agents' groups never step (HipAdam.freeze); global: the one shared net trains on the others
         self._frozen = {}
         if self.hc_mask and arch != "global":
@@ -267,6 +294,8 @@ class Trainer(EpisodeLogging):
         # streams stay independent but a split run no longer reproduces the unsplit one: say so.
         if world_size > 1 or rollout_streams > 1:
             per_group = [("acceptor", self.acc.S)] + ([] if self.free else [("offer", self.off.S)])
+            if self.auct is not None:
+                per_group.append(("auctioneer", C))
             for _, e0, _ in self.env.parts:
                 for name, S in per_group:
                     if ((rank * self.E + e0) * S) % 128:
@@ -306,6 +335,12 @@ class Trainer(EpisodeLogging):
         # of every rollout like the price table (ActFrag; bit-identical to acting without them)
         self.off_frag = ActFrag(self.off.group.policy_old, s.off_obs_stride)
         self.acc_frag = ActFrag(self.acc.group.policy_old, s.acc_obs_stride, self.acc_common)
+        # the auctioneer's states are the compact acceptor rows with this ring as the owners: 1 where nobody owns
+        # the core (derived from acc_owner by the round that acts on a slot and by the update)
+        self.auct_frag = self.auct_owner0 = None
+        if self.auct is not None:
+            self.auct_frag = ActFrag(self.auct.group.policy_old, s.acc_obs_stride, self.acc_common)
+            self.auct_owner0 = torch.zeros((T + 1, self.E, C), dtype=torch.int8, device=dev)
         self.agent_reward = torch.zeros((self.E, N), dtype=torch.int32, device=dev)
         self.auct_reward = torch.zeros((self.E, C), dtype=torch.int32, device=dev)
         self.rng = random.Random(seed)  # sub-unit draws (random.randint), identical on every rank
@@ -357,6 +392,9 @@ class Trainer(EpisodeLogging):
                            all(env.fused_act_supported() for env, _, _ in self.env.parts))
         # a mixed market: the fused launches' mixed forms (ABI 24), else an act launch and step_mixed per round
         if self.hc_mask and not all(env.fused_mixed_supported() for env, _, _ in self.env.parts):
+            self.fused_step = False
+        # a learned auctioneer: the fused launches' forms with its acting (env_auct_kernels.hip), else launch pairs
+        if self.auct is not None and not all(env.auct_supported() for env, _, _ in self.env.parts):
             self.fused_step = False
         # ... and the whole rollout's rounds are one launch (ms_env_rollout_act): each wave steps and acts
         # for its replicas round after round (MS_ENV_ROLLOUT=0: one launch per round, for A/B measurements)
@@ -470,7 +508,7 @@ class Trainer(EpisodeLogging):
         broadcast_params([u.group for u in self.units()], self.pg)
 
     def units(self):
-        return [u for u in (self.acc, self.off, self.price) if u is not None]
+        return [u for u in (self.acc, self.off, self.price, self.auct) if u is not None]
 
     # ---- rollout
     def _prepare_acting(self):
@@ -483,6 +521,8 @@ class Trainer(EpisodeLogging):
             self.price_table.build(self.price.group.policy_old)
         self.off_frag.build(self.off.group.policy_old)
         self.acc_frag.build(self.acc.group.policy_old)
+        if self.auct is not None:
+            self.auct_frag.build(self.auct.group.policy_old)
         self._acting_version = self._policy_version
 
     def round(self, t: int):
@@ -505,6 +545,8 @@ class Trainer(EpisodeLogging):
         """getActionForAllAgents of round t for replica part k (on stream k)."""
         if self.fused_step and t > 0:
             return  # sampled by round t - 1's env launch (_step_part)
+        if self.auct is not None:
+            self._act_auct_part(t, k)
         env, e0, e1 = self.env.parts[k]
         st = self.streams[k]
         E, N, C, L = e1 - e0, self.N, self.C, self.L
@@ -565,6 +607,29 @@ class Trainer(EpisodeLogging):
                                           common_row=self.acc_common if self.common_rows else None, stream=st,
                                           frag=self.acc_frag, replica_base=rb)
 
+    def _act_auct_part(self, t: int, k: int):
+        """The auctioneer's actions of round t for replica part k (on stream k): its net on the auctioneer rows,
+        which are the compact acceptor rows with "nobody owns the core" as the owner, at Philox offset 8 t + 5
+        (rounds use + 1 for the offer units and + 3 for the acceptors)."""
+        e0, e1 = self.env.parts[k][1:]
+        st = self.streams[k]
+        own0 = self.auct_owner0[t][e0:e1]
+        with torch.cuda.stream(st if st is not None else torch.cuda.current_stream(self.device)):
+            torch.eq(self.acc_owner[t][e0:e1], 0, out=own0)
+        self.auct.group.policy_old.act_compact(self.acc_rows[t][e0:e1], own0, self.C, self.seed * 7919, 8 * t + 5,
+                                               self.acc_common, action=self.auct.actions[t][e0:e1],
+                                               logprob=self.auct.logprobs[t][e0:e1], stream=st,
+                                               offset_dev=self.rng_ctr, frag=self.auct_frag,
+                                               replica_base=self.rank * self.E + e0)
+
+    def _fused_next_auct(self, t: int, k: int):
+        """Round t's acting of the auctioneer (_act_auct_part) for replica part k, as the acting fused into round
+        t - 1's env launch beside _fused_next's."""
+        e0, e1 = self.env.parts[k][1:]
+        rb = self.rank * self.E + e0
+        return abi.MsFusedActAuct(self.auct.group.policy_old.mlp_params(self.auct_frag, rb * self.C), 8 * t + 5,
+                                  ptr(self.auct.actions[t][e0:e1]), ptr(self.auct.logprobs[t][e0:e1]))
+
     def _step_part(self, t: int, k: int):
         """env.step + saveRewards of round t for replica part k (on stream k)."""
         env, e0, e1 = self.env.parts[k]
@@ -579,6 +644,15 @@ class Trainer(EpisodeLogging):
         if self._elog is not None:
             ev = dict(ev or {}, metrics=self._elog.bufs[k])
         nxt = self._fused_next(t + 1, k) if self.fused_step and t + 1 < self.T else None
+        if self.auct is not None:  # the round plays the auctioneer ring's slot and writes its per-core rewards
+            rew["auctioneer"] = sl(self.auct.rewards[t])
+            acc_t, off_t = sl(self.acc.actions[t]).view(E, N, C), sl(self.off.actions[t]).view(E, N, L)
+            if nxt is not None:
+                env.step_act_auct(acc_t, off_t, sl(self.auct.actions[t]), nxt, self._fused_next_auct(t + 1, k), obs, rew,
+                                  events=ev, stream=st)
+            else:
+                env.step(acc_t, off_t, auctioneer=sl(self.auct.actions[t]), obs=obs, rewards=rew, events=ev, stream=st)
+            return
         if self.hc_mask:  # a mixed market: the ring slot receives what the masked agents played
             acc_t, off_t = sl(self.acc.actions[t]).view(E, N, C), sl(self.off.actions[t]).view(E, N, L)
             if nxt is not None:
@@ -620,6 +694,16 @@ class Trainer(EpisodeLogging):
                                      b(self._off_obs), b(self.off.rewards), b(self.acc.rewards), 0, 0,
                                      b(self.off.actions), b(self.off.logprobs), b(self.acc.actions),
                                      b(self.acc.logprobs), 8)
+        if self.auct is not None:  # (ms_env_rollout_act_auct) the auctioneer ring is played and written
+            au = self.auct
+            rew["auctioneer"] = sl(au.rewards[0])
+            strides.auctioneer_reward = b(au.rewards)
+            astrides = abi.MsRoundStridesAuct(b(au.actions), b(au.actions), b(au.logprobs))
+            env.rollout_act_auct(sl(self.acc.actions[0]).view(E, N, C), sl(self.off.actions[0]).view(E, N, L),
+                                 sl(au.actions[0]), obs, rew, self._fused_next(1, k), self._fused_next_auct(1, k),
+                                 strides, astrides, self.T, act_after_last=False, events=ev, stream=self.streams[k],
+                                 next_out=dict(auct_action=sl(au.actions[1]), auct_logprob=sl(au.logprobs[1])))
+            return
         env.rollout_act(sl(self.acc.actions[0]).view(E, N, C), sl(self.off.actions[0]).view(E, N, L), obs, rew,
                         self._fused_next(1, k), strides, self.T, act_after_last=False, events=ev,
                         stream=self.streams[k], hardcoded=self.hc_mask or self._empty_mask)
@@ -881,6 +965,10 @@ class Trainer(EpisodeLogging):
             sel = dict(acceptor=acc, offer=off)
         sel["price"] = sel["offer"]
         host["price"] = host["offer"]
+        if getattr(self, "auct", None) is not None:  # the auctioneer's cores, after the agents' draws under every arch
+            cores = [self.rng.randint(0, C - 1) for _ in range(CS)]
+            sel["auctioneer"] = [torch.tensor([c], device=dev) for c in cores]
+            host["auctioneer"] = [[c] for c in cores]
         self._last_draws = host  # (update_diagnostics reads the rows the update drew)
         return sel
 
@@ -920,6 +1008,8 @@ class Trainer(EpisodeLogging):
         T = self.T
         if u is self.acc:
             return self.acc_rows[:T] if self.compact else self.acc_obs[:T]
+        if u is self.auct:
+            return self.acc_rows[:T]
         return (self.off_obs if u is self.off else self.price_obs)[:T]
 
     def _update_graphed(self):
@@ -1040,6 +1130,9 @@ class Trainer(EpisodeLogging):
         ret_all = unit_returns(u.rewards, sel_u, u.group.gamma)
         common = self.acc_common if (u is self.acc and self.common_rows) else None
         owner = self.acc_owner[:T].reshape(T * E, self.C) if (u is self.acc and self.compact) else None
+        if u is self.auct:  # unit c (agent 0): core row c where the derived owner is 1, else the common row
+            torch.eq(self.acc_owner[:T], 0, out=self.auct_owner0[:T])
+            common, owner = self.acc_common, self.auct_owner0[:T].reshape(T * E, self.C)
         regen = self._acc_regen_args() if (u is self.acc and self.acc_regen) else None
         rows = self._update_rows(u)
         compact = None
@@ -1095,6 +1188,10 @@ class Trainer(EpisodeLogging):
         for u in self.units():
             ls = []
             st_u = self.acceptor_rows(0, T) if (u is self.acc and self.compact) else self._states_of(u)
+            if u is self.auct:
+                from .ppo import regen_acceptor_rows
+                st_u = regen_acceptor_rows(self.acc_rows[:T], (self.acc_owner[:T] == 0).to(torch.int8),
+                                           self.acc_common, 1)
             for u_sel in sel[u.name]:
                 x, a, lp, ret = u.batch(st_u, u_sel)
                 ls += u.group.update(x, a, lp, ret)
@@ -1281,7 +1378,7 @@ class Trainer(EpisodeLogging):
 
     def evaluate(self, episodes: int = 1, n_envs: int | None = None, mode: str = "greedy", seed: int | None = None,
                  trace: bool = False, hardcoded_agents=None, action_log: bool = False,
-                 action_tables: bool = False) -> dict:
+                 action_tables: bool = False, auctioneer: str | None = None) -> dict:
         """Evaluate the current policy (policy_old, the nets the next rollout acts with) for `episodes` episodes
         of episode_length rounds on n_envs (default: E) fresh replicas of their own; replica e is seeded
         seed + e (default seed: eval_seed()). Training state is left untouched: the training env, the rings,
@@ -1310,6 +1407,14 @@ class Trainer(EpisodeLogging):
         buffers hold owners, else every unit. action_tables (needs action_log) adds the action-by-priority tables.
         ValueError with mode "hardcoded" (no action tensors exist there). The training log is not touched.
 
+        auctioneer ("learned" or "hardcoded"; default: "learned" on a trainer with learned_auctioneer, else
+        "hardcoded"): who sells the cores nobody owns. "learned": the trainer's auctioneer net acts on the emitted
+        auctioneer rows every round, the argmax under "greedy" (act_greedy with the common row) and sampled at Philox
+        offset 8 t + 5 under "sample"; "hardcoded": the in-kernel HardcodedAuctioneerAcceptor, with a learned
+        auctioneer's trainer the baseline on the same job streams. ValueError for "learned" on a trainer without a
+        learned auctioneer or with mode "hardcoded". The result's "auctioneer" records which one played; with trace
+        and a learned auctioneer the rounds gain auctioneer (its rows) / auctioneer_action.
+
         Eager launches on the current stream (one act launch and one env round per round). Each call steps a
         newly created env (an env's reset re-emits observations; it does not rewind the world or its job
         stream), so equal arguments give equal results; the tensors are kept between calls, and the last env
@@ -1318,7 +1423,7 @@ class Trainer(EpisodeLogging):
         Plot.py reads, averaged over replicas), per_replica=[[dict per replica] per episode]); with trace also
         trace=[per round: the observations acted on and every action array fed to the env, CPU tensors]."""
         return evaluation.evaluate(self, episodes, n_envs, mode, seed, trace, hardcoded_agents, action_log,
-                                   action_tables)
+                                   action_tables, auctioneer)
 
     # ---- checkpoints (checkpoint.py)
     def save_checkpoint(self, path: str) -> dict:
